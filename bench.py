@@ -2,6 +2,8 @@
 """bench.py -- phonon-steps/s of the Population timestep loop on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR    # also writes the last timed step's tallies as DIR/*.npy
+    python bench.py --full ...                       # also the extra legs, the repeats and the CPU / reference figures (below)
     python bench.py --gpus N ...                     # starts the N rank processes itself (before anything touches a GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W       # or under a launcher that sets RANK / LOCAL_RANK / WORLD_SIZE
@@ -13,13 +15,17 @@ Workload (BASELINE.json configs[1], SURVEY.md 8d "C2"): synthetic Si (31^3 q-poi
 one GPU); the default line is c2.
 A "step" is one Population.run_timestep: relax -> drift -> reservoir emission -> boundary events -> tally -> T update
 (kernels k_sweep and k_reduce with the fused update; with RCCL the all-reduce sits between k_reduce and k_update).
-Particles are resident in HBM before the timed region.  The timed region (exactly --steps steps between barriers, the
-stream drained on both sides) is repeated --repeats times; the line reports the MEDIAN repeat and the spread.
-One JSON line is printed by rank 0.  At N = 1 the line also carries the CPU legs, measured on this host with the oracle
-(a C port of the reference loop): `cpu_baseline` (one thread, 1e6 particles, after the GPU part) and
-`cpu_baseline_all_cores` (one worker process per core, forked before anything touches the GPU), plus
-`cpu_reference_numpy`, the reference's own NumPy loop as measured in the build container (a labelled constant: the
+Particles are resident in HBM before the timed region.  A plain run sets up, ramps and warms up (--ramp, --warmup), times
+ONE region of exactly --steps steps between barriers (the stream drained on both sides), writes the outputs if
+--dump-outputs is given and prints the line.
+--full runs the bench as a whole: the timed region is repeated --repeats times (default 5; the line reports the MEDIAN
+repeat and the spread), and the default line carries the `per_call`, `sustained` and `small_ensemble` legs (their sizes:
+--per-call, --sustained, --small, which also run a leg without --full).  At N = 1 a --full line also carries the CPU
+legs, measured on this host with the oracle (a C port of the reference loop): `cpu_baseline` (one thread, 1e6 particles,
+after the GPU part) and `cpu_baseline_all_cores` (one worker process per core, forked before anything touches the GPU),
+plus `cpu_reference_numpy`, the reference's own NumPy loop as measured in the build container (a labelled constant: the
 reference cannot travel to the GPU box).  --no-cpu-baseline skips the measured legs.
+One JSON line is printed by rank 0.
 
 No PyTorch anywhere: the ranks meet on a UNIX socket (nanokappa_amd.sharding.NodeRendezvous) to hand round the RCCL
 unique id, for the barriers and for the max of the elapsed times; the compute path is libnanokappa_hip.so + RCCL.
@@ -269,7 +275,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=50)
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps each; the median is reported')
+    ap.add_argument('--full', action='store_true',
+                    help='the whole bench: repeated timed regions, the per_call / sustained / small_ensemble legs of the default '
+                         'line, the CPU legs and the reference figure; a plain run times one region of --steps steps and nothing else')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step returned (the tallies of Engine.step) as DIR/<name>.npy')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of --steps steps each; the median is reported (default 5 with --full, else 1)')
     ap.add_argument('--ramp', type=int, default=400,
                     help='untimed steps right after set-up, before the --warmup steps: the device comes out of ~10 s of host-side set-up '
                          'in a low power state and its first few hundred steps (0.1 s) run 3-6 %% slower than the sustained rate')
@@ -280,16 +292,18 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--sustained', type=int, default=None,
                     help='steps of the `sustained` leg (BASELINE config 2 is quoted on 10000 iterations); default 10000 for '
-                         'the default line (c2, one GPU), 0 otherwise')
+                         'the default line (c2, one GPU) with --full, 0 otherwise')
     ap.add_argument('--per-call', type=int, default=None,
                     help='Population.run_timestep calls of the `per_call` leg (the reference driver\'s granularity); '
-                         'default 500 for the default line, 0 otherwise')
+                         'default 500 for the default line with --full, 0 otherwise')
     ap.add_argument('--small', type=int, default=None,
                     help='steps per region of the `small_ensemble` leg (BASELINE config 1 at its own 1e5 particles, launch-per-step path '
-                         'and resident kernel); default 500 for the default line, else 0')
+                         'and resident kernel); default 500 for the default line with --full, else 0')
     ap.add_argument('--calibrate', action='store_true',
                     help='after the timed region run 3 known-traffic sweeps (k_cal_stream) for PMC calibration')
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     if a.gpus < 1 or a.steps < 1 or a.repeats < 1:
         raise SystemExit('--gpus, --steps and --repeats must be positive')
 
@@ -331,11 +345,11 @@ def main():
         geo = quiet(Geometry, args)
     ph = Phonon(args, 0, material=synthetic.make_material(a.mesh_n, species, temperatures=np.arange(200.0, 401.0, 10.0)))
 
-    default_line = world == 1 and a.config == 'c2' and a.particles is None
+    default_line = a.full and world == 1 and a.config == 'c2' and a.particles is None
     n_sustained = a.sustained if a.sustained is not None else (10000 if default_line else 0)
     n_per_call = a.per_call if a.per_call is not None else (500 if default_line else 0)
     n_small = a.small if a.small is not None else (500 if default_line else 0)
-    cpu_legs = world == 1 and not a.no_cpu_baseline
+    cpu_legs = a.full and world == 1 and not a.no_cpu_baseline
     rough_cfg = a.config in ('c1b', 'c4')
     all_cores = None
     if cpu_legs and not rough_cfg:
@@ -362,11 +376,12 @@ def main():
 
     for _ in range(max(a.ramp, 0) // 100):
         eng.step(100)                      # the ramp (see --ramp): the same steps, untimed
-    if a.warmup > 0:
-        eng.step(a.warmup)                 # nk_step returns after the stream has drained (hipStreamSynchronize)
-    # one untimed region with the timed regions' own call pattern (same --steps): first-use costs of that pattern (history
-    # buffer, event pool, clocks) land here, not in the first timed region
-    eng.step(a.steps)
+    # the warm-up in calls of at most --steps steps, the timed call's own pattern: first-use costs of that pattern (history
+    # buffer, event pool, clocks) land here, not in the timed region; nk_step returns after the stream has drained
+    for k in range(0, max(a.warmup, 0), a.steps):
+        eng.step(min(a.steps, a.warmup - k))
+    if a.full:
+        eng.step(a.steps)                  # one more untimed region of the timed regions' length before the repeats
     runs = []
     for _ in range(a.repeats):
         tm0 = eng.timing()
@@ -377,6 +392,11 @@ def main():
         elapsed = rdv.max(time.perf_counter() - t0)
         tm = eng.timing()
         runs.append(dict(elapsed=elapsed, psteps=float(t['N_sv'].sum()), tm=tm, hk=housekeeping(tm0, tm)))   # N_sv: all ranks (all-reduced)
+    if a.dump_outputs and rank == 0:
+        # what Engine.step returned to rank 0 for the last timed step: tallies per subvolume and reservoir (float64, a few KB)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in t.items():
+            np.save(os.path.join(a.dump_outputs, name + '.npy'), np.asarray(arr[-1], dtype=np.float64))
     if a.calibrate:
         cal = eng.calibrate_stream(3)
         if rank == 0:
@@ -477,8 +497,10 @@ def main():
             # but not here lost its time on the host (launch thread descheduled), not in a kernel
             'stream_ms_per_step_repeats': [r['tm']['total_ms'] / a.steps for r in runs],
             'timing': 'median of %d timed regions of %d steps each (barrier + drained stream on both sides, max over ranks); %d warm-up '
-                      'steps and one untimed region of %d steps before them, behind an untimed ramp of %d steps after set-up (--ramp: the '
-                      'device leaves the host-side set-up in a low power state)' % (a.repeats, a.steps, a.warmup, a.steps, max(a.ramp, 0) // 100 * 100),
+                      'steps in calls of at most %d%s before them, behind an untimed ramp of %d steps after set-up (--ramp: the '
+                      'device leaves the host-side set-up in a low power state)'
+                      % (a.repeats, a.steps, a.warmup, a.steps, ' and one untimed region of %d steps' % a.steps if a.full else '',
+                         max(a.ramp, 0) // 100 * 100),
             'ramp_steps': max(a.ramp, 0) // 100 * 100,
             'config': {'workload': '%s-like synthetic %d^3x6 modes, %s, dt 1 ps, %.3g particles per GPU (BASELINE config %s)'
                                    % (species, a.mesh_n, desc, per_gpu, a.config),
@@ -524,7 +546,8 @@ def main():
             out['cpu_baseline'] = cpu_baseline(geo, ph, a.mesh_n, desc, n=n_cpu, rough=rough)
             if all_cores is not None:
                 out['cpu_baseline_all_cores'] = all_cores
-        out['cpu_reference_numpy'] = CPU_REFERENCE_NUMPY
+        if a.full:
+            out['cpu_reference_numpy'] = CPU_REFERENCE_NUMPY
         print(json.dumps(out))
         sys.stdout.flush()
     rdv.barrier()

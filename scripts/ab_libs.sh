@@ -7,7 +7,7 @@ out=gpurun_out/$tag; mkdir -p $out
 for lib in $libs; do for c in $cfgs; do
   n=$(ls $out 2>/dev/null | grep -c "^${lib}_${c}_") 
   f=$out/${lib}_${c}_$n
-  NK_VERBOSE=1 NK_LIBNAME=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 20 --config $c "$@" > $f.json 2> $f.err || { echo "FAILED $lib $c"; tail -5 $f.err; exit 1; }
+  NK_VERBOSE=1 NK_LIBNAME=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 20 --config $c "$@" > $f.json 2> $f.err || { echo "FAILED $lib $c"; tail -5 $f.err; exit 1; }
   python - "$f.json" "$lib" "$c" <<'PY'
 import json,sys
 j=json.load(open(sys.argv[1])); r=j['roofline']

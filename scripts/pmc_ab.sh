@@ -13,7 +13,7 @@ for lib in $libs; do for c in $cfgs; do
   i=0
   for G in "$G1" "$G2"; do
     i=$((i+1))
-    NK_LIBNAME=$lib timeout -k 5 200 rocprofv3 --kernel-trace --pmc $G -d $O/${lib}_${c}_g$i -o p --output-format csv -- python3 $R/bench.py --config $c --steps 10 --warmup 5 --repeats 1 --no-cpu-baseline > /dev/null 2> $O/${lib}_${c}_g$i.log
+    NK_LIBNAME=$lib timeout -k 5 200 rocprofv3 --kernel-trace --pmc $G -d $O/${lib}_${c}_g$i -o p --output-format csv -- python3 $R/bench.py --full --config $c --steps 10 --warmup 5 --repeats 1 --no-cpu-baseline > /dev/null 2> $O/${lib}_${c}_g$i.log
     echo "$lib $c group $i rc $?" | tee -a $O/progress.txt
   done
 done; done

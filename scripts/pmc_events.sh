@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/pmc_events
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --config c4 --particles 1e7 --steps 6 --warmup 2 --repeats 1 --no-cpu-baseline"
+B="python3 $R/bench.py --full --config c4 --particles 1e7 --steps 6 --warmup 2 --repeats 1 --no-cpu-baseline"
 i=0
 # (a pass that asks a block for more counters than it has aborts inside rocprofv3 -- "Request exceeds the capabilities of the
 # hardware to collect" -- and the aborted process then hangs in the tool's signal handler: two counters per block and pass,

@@ -2,7 +2,7 @@
 # The resident kernel at 1e5 / 1e6 particles with its clock marks (NK_VERBOSE), beside the launch-per-step path.  gpurun -- 'bash scripts/resident_probe.sh tag [mesh-n]'
 R=$GRAFT_REPO_ROOT; tag=$1; O=$R/gpurun_out/$tag; mkdir -p $O; MESH=${2:-31}
 run() { name=$1; shift; ( for e in "$@"; do [[ "$e" == *=* ]] && export $e; done
-  timeout -k 10 200 python3 $R/bench.py --particles $N --mesh-n $MESH --steps 200 --warmup 100 --repeats 3 --no-cpu-baseline --sustained 0 --per-call 0 --small 0 --ramp 0 > $O/$name.json 2> $O/$name.err ); echo "$name rc $?"; }
+  timeout -k 10 200 python3 $R/bench.py --full --particles $N --mesh-n $MESH --steps 200 --warmup 100 --repeats 3 --no-cpu-baseline --sustained 0 --per-call 0 --small 0 --ramp 0 > $O/$name.json 2> $O/$name.err ); echo "$name rc $?"; }
 for N in 100000 1000000; do
   run n${N}_resident NK_RESIDENT=1 NK_RESIDENT_MAX=100000000 NK_VERBOSE=1
   grep "resident step" $O/n${N}_resident.err | tail -2

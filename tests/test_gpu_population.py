@@ -338,13 +338,13 @@ def test_parameter_file_front_end(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_line_carries_a_finite_kappa_with_the_drivers_arguments():
-    """`bench.py --steps 20 --warmup 5` steps the engine 525 times before the sustained leg; the rows of
+    """`bench.py --full --steps 20 --warmup 5` steps the engine 525 times before the sustained leg; the rows of
     that leg must still land on steps whose flux the library tallied (one step clock, tests/test_step_clock.py).  A reduced
     ensemble and material keep this a matter of seconds; the code path is the default line's."""
     import json
     import subprocess
     root = os.path.join(os.path.dirname(__file__), '..')
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '1', '--steps', '20', '--warmup', '5',
                         '--particles', '300000', '--mesh-n', '9', '--sustained', '300', '--per-call', '25', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -82,7 +82,7 @@ def build(tmp_path=None):
 
 @pytest.mark.parametrize('behind_the_back', [525, 7, 0, 1000])
 def test_rows_land_on_flux_steps_after_direct_engine_steps(behind_the_back):
-    """The driver's bench invocation steps the engine 400 + 5 + 20 + 5 x 20 = 525 times before Population.run: every
+    """`bench.py --full` with the driver's arguments steps the engine 400 + 5 + 20 + 5 x 20 = 525 times before Population.run: every
     convergence row must still carry a finite flux and kappa."""
     pop, geo, ph, eng = build()
     if behind_the_back:
