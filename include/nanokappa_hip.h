@@ -153,7 +153,8 @@ typedef struct {
 typedef struct {
     double step_kernel_ms;   /* mean duration of k_sweep: relax + drift + boundary events + emission + tally */
     double emit_kernel_ms;   /* mean duration of the reservoir emission (k_emit; + k_emit_one_to_one for that generator) */
-    double events_kernel_ms; /* mean duration of the step's tail: k_reduce (+ all-reduce) + k_update */
+    double events_kernel_ms; /* mean duration of the step's tail: k_reduce (+ all-reduce) + k_update (+ the band pass of
+                              * nk_set_bands on heat-flux steps) */
     double total_ms;         /* wall time of the whole call on the stream */
     int64_t slots;           /* particle capacity (nseg * segcap) */
     int64_t live;            /* live particles after the call (this rank) */
@@ -244,6 +245,26 @@ int nk_comm_info(nk_ctx *ctx, nk_comm_report *out);
 /* Sum of a small host vector over the ranks of the communicator (in place; unchanged when there is none): the t = 0 tallies
  * of the shards (Population.py:282, :318-321 on an ensemble that is spread over the ranks). */
 int nk_comm_allreduce(nk_ctx *ctx, double *inout, int64_t n);
+
+/* Frequency-resolved conductivity (reference Visualisation.flux_contribution, Visualisation.py:592-651): the heat flux tallied
+ * per subvolume AND band.  band_of_mode [M] gives the band (0 .. nbands - 1, or -1 for none) of every global mode index q*J+j;
+ * what a band is (frequency, branch, mean free path) is the caller's choice.  nbands = 0 turns the feature off (the default):
+ * then nothing is launched or allocated for it.  Needs nk_set_material and nk_set_subvolumes; NK_ERR_ARG when the S x nbands
+ * bins do not fit the pass's LDS even one band at a time.  While bands are on, the resident kernel (NK_RESIDENT) is not used.
+ * Rows: F [S][nbands][3] = sum of v_i e_i and N [S][nbands] = particle counts, e_i = hbar omega_i (n_i - n0) exactly as the
+ * flux_raw row computes it, so that sum over the bands of F[s] = flux_raw[s] of the same step (up to the order of the sums). */
+int nk_set_bands(nk_ctx *ctx, int32_t nbands, const int32_t *band_of_mode);
+/* The rows of the heat-flux steps of the last nk_step call ((step + 1) % flux_every == 0), tallied after the step's sweep --
+ * the particles and occupations that step's flux_raw summed, against the same temperatures -- and the absolute step of each.
+ * A heat-flux step at which migrating particles (rough facets) did not fit their new segment, so that the store grows before
+ * they are delivered, has no row: the pass did not see them.  The pass is timed with the tail (events_kernel_ms).
+ * F [nrows*S*nbands*3], N [nrows*S*nbands], steps [nrows]; any may be NULL; *nrows receives the count (cap 0: query only;
+ * otherwise cap must hold every row).  Summed over all ranks (one all-reduce per nk_step call) once nk_comm_init was called. */
+int nk_get_band_rows(nk_ctx *ctx, double *F, double *N, int64_t *steps, int32_t cap, int32_t *nrows);
+/* The same sums for the particles where they stand, after the deferred relaxation, with n0 at each particle's interpolated
+ * temperature (the one the relaxation uses; the reference's Population.temperatures) and the current T_sv:
+ * F [S*nbands*3], N [S*nbands], summed over the ranks with a communicator. */
+int nk_tally_bands_state(nk_ctx *ctx, double *F, double *N);
 
 /* device versions of the reference's primitives, for parity tests (tests/ -m gpu) */
 int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,

@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Two additions: `--seed` (the reference uses the unseeded global NumPy generator) and `--device`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device` and `--spectral_bands`."""
 import argparse
 import os
 import sys
@@ -49,6 +49,9 @@ def initialise_parser(debug_flag=False):
     # additions of this build
     a('--seed', default=[0], type=int, nargs=1, help='seed of the counter-based RNG (Philox4x32-10)')
     a('--device', default=[0], type=int, nargs=1, help='HIP device index')
+    a('--spectral_bands', default=['0', 'frequency'], type=str, nargs='*',
+      help='N [frequency|branch] (or just: branch): tally the heat flux in N frequency bands, or one band per branch, on '
+           'every heat-flux step and write the frequency-resolved conductivity to k_contribution.txt; 0 = off')
     return p
 
 

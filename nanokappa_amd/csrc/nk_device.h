@@ -1136,13 +1136,18 @@ __device__ __forceinline__ int nk_event_one(const NkDev &d, int NG, const double
     return nk_event_post(d, p, cts, ev, tc, fcn);
 }
 
+// The energy a particle in subvolume s carries above the reference (Population.py:715-717): e = hbar omega (n - n0), n0 at the
+// subvolume's temperature ('local') or at the fixed reference.  Shared by the tally and the band-resolved pass (k_spectral).
+__device__ __forceinline__ double nk_tally_e(const NkDev &d, const NkSvTab &tb, int s, double occ, double omega, double E0) {
+    const double n0 = d.T_ref_local ? nk_be(omega * d.c_hk, E0, tb.sv[s].invT, d.invT0) : nk_occupation(d, d.T_ref, omega, E0);
+    return d.hbar * omega * (occ - n0);
+}
 // Population.calculate_energy's per-particle part (Population.py:704-717) + the heat-flux sum (:734-736).
 __device__ __forceinline__ void nk_tally_one(const NkDev &d, const NkSvTab &tb, NkBins &b, double x, double y, double z,
                                              double occ, double omega, double E0, double vx, double vy, double vz,
                                              bool do_flux, int rep) {
     const int s = nk_classify(d, tb, x, y, z);
-    const double n0 = d.T_ref_local ? nk_be(omega * d.c_hk, E0, tb.sv[s].invT, d.invT0) : nk_occupation(d, d.T_ref, omega, E0);
-    const double e = d.hbar * omega * (occ - n0);
+    const double e = nk_tally_e(d, tb, s, occ, omega, E0);
     atomicAdd(&b.E[rep * d.S + s], e);
     atomicAdd(&b.N[rep * d.S + s], 1u);
     if (do_flux) {

@@ -126,6 +126,15 @@ struct nk_ctx {
     const double *d_omega = nullptr, *d_vg = nullptr;   // kept to rebuild the packed mode records
     std::vector<double> h_Tgrid;
     double T_lo = 0.0, T_hi = 0.0;      // range of the subvolume temperatures last seen by the host
+    // band-resolved heat flux (nk_set_bands, k_spectral): off while band_B == 0 -- then nothing is launched or allocated
+    int32_t band_B = 0;                  // bands
+    int32_t *band_map = nullptr;         // [M] band of every mode, -1 = none
+    double *band_slabs = nullptr;        // per-workgroup partial slabs of k_spectral
+    size_t band_slabs_n = 0;
+    double *band_rows_d = nullptr;       // reduced rows of a batch's heat-flux steps, [rows][4 S B]
+    size_t band_rows_n = 0;
+    std::vector<double> band_rows;       // the rows of the last nk_step call: F [S][B][3], then N [S][B]
+    std::vector<int64_t> band_steps;     //   and the absolute step of each
 };
 
 #define NK_HIP(call)                                                                                   \
@@ -432,6 +441,9 @@ void nk_destroy(nk_ctx *ctx) {
     if (ctx->mig_n) hipFree(ctx->mig_n);
     if (ctx->ep_p) hipFree(ctx->ep_p);
     if (ctx->rc_p) hipFree(ctx->rc_p);
+    if (ctx->band_map) hipFree(ctx->band_map);
+    if (ctx->band_slabs) hipFree(ctx->band_slabs);
+    if (ctx->band_rows_d) hipFree(ctx->band_rows_d);
     hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1840,6 +1852,51 @@ static int nk_flush_relax(nk_ctx *ctx, int honor_halt) {
     return NK_OK;
 }
 
+// ---- band-resolved heat flux (k_spectral, nk_kernels.h).  A workgroup keeps S x Bt bins of 28 B in LDS behind the subvolume
+// tables, within the 64 KB a launch gets without asking; a table of more bands is done in tiles of Bt bands, one pass each.
+static inline size_t nk_band_lds0(const nk_ctx *ctx) { return (nk_lds(ctx, false) + 15) & ~(size_t)15; }
+static inline int nk_band_tile(const nk_ctx *ctx) {
+    const size_t l0 = nk_band_lds0(ctx), per = (size_t)ctx->d.S * 28;
+    if (l0 >= 65536 || per == 0) return 0;
+    return (int)std::min<size_t>((65536 - l0) / per, (size_t)ctx->band_B);
+}
+static inline int nk_band_grid(const nk_ctx *ctx) { return std::max(1, std::min(2 * ctx->num_cu, (int)ctx->d.nseg)); }
+// slabs for one pass and `rows` reduced rows on the device
+static int nk_band_ensure(nk_ctx *ctx, int rows) {
+    const int S = ctx->d.S, B = ctx->band_B, Bt = nk_band_tile(ctx);
+    NK_ARG(Bt > 0, "band-resolved flux: the subvolume tables leave no room for one band's bins in 64 KB of LDS");
+    const size_t ns = (size_t)nk_band_grid(ctx) * 4 * S * Bt, nr = (size_t)rows * 4 * S * B;
+    if (ns > ctx->band_slabs_n) {
+        if (ctx->band_slabs) hipFree(ctx->band_slabs);
+        ctx->band_slabs = nullptr; ctx->band_slabs_n = 0;
+        NK_HIP(hipMalloc((void **)&ctx->band_slabs, ns * sizeof(double)));
+        ctx->band_slabs_n = ns;
+    }
+    if (nr > ctx->band_rows_n) {
+        if (ctx->band_rows_d) hipFree(ctx->band_rows_d);
+        ctx->band_rows_d = nullptr; ctx->band_rows_n = 0;
+        NK_HIP(hipMalloc((void **)&ctx->band_rows_d, nr * sizeof(double)));
+        ctx->band_rows_n = nr;
+    }
+    return NK_OK;
+}
+// One band row [4 S B] into row_dev: k_spectral + k_spectral_reduce per tile of bands (step mode honours the halt word).
+static int nk_band_pass(nk_ctx *ctx, bool state, double *row_dev) {
+    const NkDev &d = ctx->d;
+    const int S = d.S, B = ctx->band_B, Bt = nk_band_tile(ctx), G = nk_band_grid(ctx);
+    const size_t l0 = nk_band_lds0(ctx);
+    for (int b0 = 0; b0 < B; b0 += Bt) {
+        const int bt = std::min(Bt, B - b0);
+        const size_t lds = l0 + (size_t)S * bt * 28;
+        if (state) k_spectral<true><<<G, NK_SPEC_WG, lds, ctx->stream>>>(d, ctx->band_map, b0, bt, (int)l0, ctx->band_slabs);
+        else k_spectral<false><<<G, NK_SPEC_WG, lds, ctx->stream>>>(d, ctx->band_map, b0, bt, (int)l0, ctx->band_slabs);
+        const int nc = 4 * S * bt;
+        k_spectral_reduce<<<(nc + 3) / 4, 256, 0, ctx->stream>>>(state ? nullptr : d.halt, ctx->band_slabs, G, S, B, b0, bt, row_dev);
+    }
+    NK_HIP(hipGetLastError());
+    return NK_OK;
+}
+
 // Enqueue up to `nsteps` timesteps without host synchronisation, drain the stream, copy the history rows back.  A sweep that
 // sees a segment which COULD overflow at the following step raises the halt word; the remaining steps of the batch then do
 // nothing, *done < nsteps comes back, and nk_step grows the store (state intact, nothing dropped) and carries on.
@@ -1912,6 +1969,15 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     const bool alt = d.seg_lo && gm_ == 1 && !split_ && !getenv("NK_NO_ALTERNATE");
     if (!alt) { int rcn_ = nk_normalize(ctx); if (rcn_) return rcn_; }
     d.down = 0;
+    // band-resolved heat flux: one row per heat-flux step of the batch (k_spectral after the sweep; nothing when off)
+    const bool bands_ = ctx->band_B > 0;
+    std::vector<int> band_s;                                  // batch step of each row
+    if (bands_) {
+        const int fe = ctx->params.flux_every;
+        int nflux = 0;
+        for (int s = 0; s < nsteps; ++s) nflux += (fe > 0 && ((ctx->step + s + 1) % fe) == 0) ? 1 : 0;
+        if (nflux > 0) { int rcb_ = nk_band_ensure(ctx, nflux); if (rcb_) return rcb_; }
+    }
     for (int s = 0; s < nsteps; ++s) {
         const int64_t stepno = ctx->step + s;
         const uint32_t step = (uint32_t)stepno;
@@ -1952,6 +2018,13 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
         // emission, in the tail launch, appends behind them)
         if (d.mig_buf) k_deliver<<<g_emit, NK_WG, 0, ctx->stream>>>(d, 1);
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s + 2], ctx->stream));
+        // the band-resolved flux of the particles the sweep has just tallied (before the tail: T_sv still the tally's; timed
+        // with the tail, nk_timing.events_kernel_ms)
+        if (bands_ && do_flux) {
+            int rcb_ = nk_band_pass(ctx, false, ctx->band_rows_d + band_s.size() * 4 * (size_t)S * ctx->band_B);
+            if (rcb_) return rcb_;
+            band_s.push_back(s);
+        }
         double *hrow = ctx->hist + (size_t)s * HROW;
         const bool ahead = tail_emit;                          // the next step's emission beside this step's tail (the last step's too: for the next call)
         if (ctx->comm) {
@@ -2089,6 +2162,20 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     int32_t nd = 0;
     while (nd < nsteps && h[(size_t)nd * HROW + NB + 2 * S + 1] != 0.0) ++nd;
     *done = nd;
+    if (!band_s.empty()) {                                   // the band rows of the steps that ran
+        const size_t rl = 4 * (size_t)S * ctx->band_B;
+        std::vector<double> br(band_s.size() * rl);
+        NK_HIP(hipMemcpyAsync(br.data(), ctx->band_rows_d, br.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        NK_HIP(hipStreamSynchronize(ctx->stream));
+        // a step whose migrants did not all fit their segments (k_deliver: halt word 2, the store grows before they are
+        // delivered) has tallied particles the pass could not see: no row for it
+        const int unseen = ctx->halt_words[2] ? nd - 1 : -1;
+        for (size_t r = 0; r < band_s.size(); ++r) {
+            if (band_s[r] >= nd || band_s[r] == unseen) continue;
+            ctx->band_rows.insert(ctx->band_rows.end(), br.begin() + r * rl, br.begin() + (r + 1) * rl);
+            ctx->band_steps.push_back(ctx->step + band_s[r]);
+        }
+    }
     {   // the emission that ran ahead in the last tail is good for the next call unless the batch halted (the store grows first)
         int32_t hw_[4];
         memcpy(hw_, ctx->halt_words, 16);
@@ -2125,6 +2212,7 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
 static inline bool nk_want_resident(const nk_ctx *ctx) {
     const NkDev &d = ctx->d;
     if (!getenv("NK_RESIDENT") || getenv("NK_NO_RESIDENT") || ctx->comm || d.nranks != 1 || d.Fr > 0 || d.mig_buf || d.qx || nk_geom_mode(ctx) != 1) return false;
+    if (ctx->band_B > 0) return false;                 // the band-resolved flux pass runs between the launches of nk_step_batch
     if (d.res_gen == 2 || d.sv_interp == 3 || d.NB > 254 || d.S > 128 || d.nseg <= 0) return false;
     const int64_t lim = getenv("NK_RESIDENT_MAX") ? atoll(getenv("NK_RESIDENT_MAX")) : 1200000;
     return d.cap <= lim && nk_lds(ctx, true, 5) <= 160 * 1024;
@@ -2253,6 +2341,8 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
     int grown = 0;
     std::vector<double> h;
     double last_T[2] = {0, 0};
+    ctx->band_rows.clear();
+    ctx->band_steps.clear();
     while (s_out < nsteps) {
         int32_t nd = 0;
         if ((rc = nk_want_resident(ctx) ? nk_step_resident(ctx, nsteps - s_out, h, &nd) : nk_step_batch(ctx, nsteps - s_out, h, &nd))) return rc;
@@ -2333,6 +2423,9 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
         ctx->err = "particle capacity exceeded during nk_step (reason mask " + std::to_string(overflow) +
                    "): particles were dropped; call nk_reserve with a larger capacity";
         return NK_ERR_CAPACITY;
+    }
+    if (ctx->comm && !ctx->band_rows.empty()) {          // the band rows of the call: summed over the ranks in one all-reduce
+        if ((rc = nk_comm_allreduce(ctx, ctx->band_rows.data(), (int64_t)ctx->band_rows.size()))) return rc;
     }
     return NK_OK;
 }
@@ -2593,6 +2686,79 @@ int nk_tally_state(nk_ctx *ctx, double *E_raw, double *N_sv, double *flux_raw) {
     const int S = d.S;
     for (int s_ = 0; s_ < S; ++s_) { E_raw[s_] = h[(size_t)s_]; N_sv[s_] = h[(size_t)S + s_]; }
     for (int k = 0; k < 3 * S; ++k) flux_raw[k] = h[(size_t)2 * S + k];
+    return NK_OK;
+}
+
+int nk_set_bands(nk_ctx *ctx, int32_t nbands, const int32_t *band_of_mode) {
+    NK_ARG(ctx && nbands >= 0, "nk_set_bands: bad arguments");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->band_map) hipFree(ctx->band_map);
+    if (ctx->band_slabs) hipFree(ctx->band_slabs);
+    if (ctx->band_rows_d) hipFree(ctx->band_rows_d);
+    ctx->band_map = nullptr; ctx->band_slabs = nullptr; ctx->band_rows_d = nullptr;
+    ctx->band_slabs_n = ctx->band_rows_n = 0;
+    ctx->band_B = 0;
+    ctx->band_rows.clear();
+    ctx->band_steps.clear();
+    if (nbands == 0) return NK_OK;
+    NK_ARG(band_of_mode, "nk_set_bands: band_of_mode is NULL");
+    NK_ARG(ctx->have_material && ctx->have_sv, "nk_set_bands: set the material and the subvolumes first");
+    const int M = ctx->d.M;
+    for (int m = 0; m < M; ++m) NK_ARG(band_of_mode[m] >= -1 && band_of_mode[m] < nbands, "nk_set_bands: a band index is out of range");
+    ctx->band_B = nbands;
+    if (nk_band_tile(ctx) <= 0) {
+        ctx->band_B = 0;
+        ctx->err = "nk_set_bands: " + std::to_string(ctx->d.S) + " subvolumes leave no room for one band's bins in 64 KB of LDS";
+        return NK_ERR_ARG;
+    }
+    hipError_t e = hipMalloc((void **)&ctx->band_map, (size_t)M * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(ctx->band_map, band_of_mode, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        ctx->band_B = 0;
+        ctx->err = std::string("nk_set_bands: ") + hipGetErrorString(e);
+        return NK_ERR_HIP;
+    }
+    return NK_OK;
+}
+
+int nk_get_band_rows(nk_ctx *ctx, double *F, double *N, int64_t *steps, int32_t cap, int32_t *nrows) {
+    NK_ARG(ctx && nrows && cap >= 0, "nk_get_band_rows: bad arguments");
+    const int32_t n = (int32_t)ctx->band_steps.size();
+    *nrows = n;
+    if (n == 0 || cap == 0) return NK_OK;
+    NK_ARG(cap >= n, "nk_get_band_rows: cap is smaller than the number of rows");
+    const size_t sb = (size_t)ctx->d.S * ctx->band_B, rl = 4 * sb;
+    for (int32_t r = 0; r < n; ++r) {
+        const double *row = ctx->band_rows.data() + r * rl;
+        if (F) memcpy(F + r * 3 * sb, row, 3 * sb * sizeof(double));
+        if (N) memcpy(N + r * sb, row + 3 * sb, sb * sizeof(double));
+        if (steps) steps[r] = ctx->band_steps[(size_t)r];
+    }
+    return NK_OK;
+}
+
+int nk_tally_bands_state(nk_ctx *ctx, double *F, double *N) {
+    NK_ARG(ctx && F && N, "nk_tally_bands_state: bad arguments");
+    NK_ARG(ctx->band_B > 0, "nk_tally_bands_state: no bands were set (nk_set_bands)");
+    int rc = nk_check_ready(ctx);
+    if (rc) return rc;
+    NK_HIP(hipSetDevice(ctx->device));
+    NkDev &d = ctx->d;
+    if ((rc = nk_normalize(ctx))) return rc;
+    if (ctx->pending_relax) {                          // the state the caller means includes the deferred relaxation
+        k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 0);
+        ctx->pending_relax = false;
+    }
+    if ((rc = nk_band_ensure(ctx, 1))) return rc;
+    if ((rc = nk_band_pass(ctx, true, ctx->band_rows_d))) return rc;
+    const size_t sb = (size_t)d.S * ctx->band_B;
+    std::vector<double> h(4 * sb);
+    NK_HIP(hipMemcpyAsync(h.data(), ctx->band_rows_d, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->comm && (rc = nk_comm_allreduce(ctx, h.data(), (int64_t)h.size()))) return rc;
+    memcpy(F, h.data(), 3 * sb * sizeof(double));
+    memcpy(N, h.data() + 3 * sb, sb * sizeof(double));
     return NK_OK;
 }
 

@@ -2076,6 +2076,91 @@ NK_KERNEL_LINKAGE __global__ __launch_bounds__(NK_WG) void k_tally_state(NkDev d
     nk_lds_flush(d, L, blockIdx.x);
 }
 
+// =================================================================================== band-resolved heat flux
+// The frequency-resolved conductivity of the reference (Visualisation.flux_contribution, Visualisation.py:592-651) needs, per
+// subvolume s and band b (band_of_mode: the host's table, -1 = in no band), F[s][b] = sum v e and N[s][b] = particles.  A pass
+// of its own over the store, which it only reads:
+//   STATE = false (step mode): right after the sweep of a heat-flux step (and k_events_end / k_deliver).  The store then holds
+//     exactly the particles the sweep tallied, with the occupations it tallied (the relaxation is deferred), and d.T_sv is still
+//     the temperature row the tally used; e is nk_tally_e's, so sum_b F[s][b] = flux_raw[s] up to the order of the sums.  The
+//     segments are walked where the sweep left them: [seg_lo, seg_lo + seg_count).
+//   STATE = true: a snapshot after the relaxation, e against the occupation at the particle's interpolated temperature (the
+//     one the relaxation uses; Visualisation.py:598-603 takes Population.temperatures).
+// Bands b0 .. b0 + Bt - 1 per launch (the host tiles wider tables): S x Bt bins {F x, F y, F z} (f64) and N (u32) in LDS at
+// byte offset lds0, behind the subvolume tables; then one slab of 4 S Bt doubles per workgroup, written with plain stores, that
+// k_spectral_reduce adds up in a fixed order.  No global atomics.
+#define NK_SPEC_WG 1024
+template <bool STATE>
+__global__ __launch_bounds__(NK_SPEC_WG) void k_spectral(NkDev d, const int32_t *band_of_mode, int b0, int Bt, int lds0, double *slabs) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (!STATE && d.halt[0]) return;                 // a halted batch: the sweep did nothing at this step
+    NkLds L;
+    nk_lds_setup<0, 0>(d, smem, L);
+    const int nb = d.S * Bt;
+    double *bF = (double *)(smem + lds0);
+    unsigned int *bN = (unsigned int *)(bF + 3 * nb);
+    for (int i = threadIdx.x; i < 3 * nb; i += blockDim.x) bF[i] = 0.0;
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) bN[i] = 0u;
+    __syncthreads();
+    const uint32_t lbmask = (1u << d.lb) - 1u;
+    for (int seg = blockIdx.x; seg < d.nseg; seg += gridDim.x) {
+        const int64_t base = (int64_t)seg * d.segcap + (d.seg_lo ? d.seg_lo[seg] : 0);
+        const int count = d.seg_count[seg];
+        const NkSegModes sm = nk_seg_modes(d, seg);
+        for (int k = threadIdx.x; k < count; k += blockDim.x) {
+            const int64_t i = base + k;
+            const int idx = (int)(d.w0[i] & lbmask);
+            const int b = band_of_mode[sm.mode(idx)] - b0;
+            if ((unsigned)b >= (unsigned)Bt) continue;
+            const NkMode *rec = sm.rec + idx;
+            const double x = d.x[i], y = d.y[i], z = d.z[i];
+            const int s = nk_classify(d, L.tb, x, y, z);
+            double e;
+            if (STATE) {
+                double invT;
+                const double T = nk_interp_T(d, L.tb, x, y, z, invT);
+                const double n0 = !d.T_ref_local ? nk_occupation(d, d.T_ref, rec->omega, rec->E0)
+                                                 : (T > 0.0 ? nk_be(rec->omega * d.c_hk, rec->E0, invT, d.invT0) : 0.0);
+                e = d.hbar * rec->omega * (d.occ[i] - n0);
+            } else {
+                e = nk_tally_e(d, L.tb, s, d.occ[i], rec->omega, rec->E0);
+            }
+            const int q = s * Bt + b;
+            atomicAdd(bF + 3 * q + 0, rec->vx * e);
+            atomicAdd(bF + 3 * q + 1, rec->vy * e);
+            atomicAdd(bF + 3 * q + 2, rec->vz * e);
+            atomicAdd(bN + q, 1u);
+        }
+    }
+    __syncthreads();
+    double *out = slabs + (int64_t)blockIdx.x * 4 * nb;
+    for (int c = threadIdx.x; c < 3 * nb; c += blockDim.x) out[c] = bF[c];
+    for (int c = threadIdx.x; c < nb; c += blockDim.x) out[3 * nb + c] = (double)bN[c];
+}
+// Column sums of the G slabs of k_spectral, one wave per column, slabs in a fixed order (lane g takes slabs g, g + 64, ...; then
+// a fixed shuffle tree): the band row F[S][B][3], N[S][B] of bands b0 .. b0 + Bt - 1.  halt: skip (halted batch) when *halt != 0.
+NK_KERNEL_LINKAGE __global__ __launch_bounds__(256) void k_spectral_reduce(const int32_t *halt, const double *slabs, int G, int S, int B,
+                                                                           int b0, int Bt, double *row) {
+    if (halt && halt[0]) return;
+    const int nb = S * Bt, lane = threadIdx.x & 63;
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= 4 * nb) return;                          // (whole waves)
+    double v = 0.0;
+    for (int g = lane; g < G; g += 64) v += slabs[(int64_t)g * 4 * nb + c];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) {
+        int64_t o;
+        if (c < 3 * nb) {
+            const int q = c / 3, k = c - 3 * q, s = q / Bt, bl = q - s * Bt;
+            o = ((int64_t)s * B + b0 + bl) * 3 + k;
+        } else {
+            const int q = c - 3 * nb, s = q / Bt, bl = q - s * Bt;
+            o = 3 * (int64_t)S * B + (int64_t)s * B + b0 + bl;
+        }
+        row[o] = v;
+    }
+}
+
 // contains_check (Population.py:1712-1722) + Mesh.sample_volume (Mesh.py:890-904)
 template <int GEOM>
 __global__ __launch_bounds__(NK_WG) void k_contains(NkDev d, uint32_t step) {

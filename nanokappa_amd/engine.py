@@ -87,7 +87,8 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_find_boundary', 'nk_classify', 'nk_eval', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
            'nk_specular_begin', 'nk_specular_pairs', 'nk_specular_end', 'nk_rough_begin', 'nk_rough_pairs', 'nk_rough_finish',
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
-           'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce']
+           'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
+           'nk_tally_bands_state']
 
 _lib = None
 
@@ -144,6 +145,9 @@ def load_library():
     L.nk_kspec_pairs.argtypes = [C.c_void_p, c_dp, C.c_int64, c_ip, c_ip, C.POINTER(C.c_int64)]
     L.nk_rough_download.argtypes = [C.c_void_p, c_dp, c_up, c_ip, c_dp]
     L.nk_build_enter_prob.argtypes = [C.c_void_p, C.c_int32, c_dp, c_dp, C.c_double, c_dp]
+    L.nk_set_bands.argtypes = [C.c_void_p, C.c_int32, c_ip]
+    L.nk_get_band_rows.argtypes = [C.c_void_p, c_dp, c_dp, C.POINTER(C.c_int64), C.c_int32, c_ip]
+    L.nk_tally_bands_state.argtypes = [C.c_void_p, c_dp, c_dp]
     _lib = L
     return L
 
@@ -212,6 +216,7 @@ class Engine(object):
             raise NkError('nk_create failed (%d): %s' % (rc, self.L.nk_last_error(None).decode()))
         self.h = h
         self.S = self.R = self.J = self.M = 0
+        self.nbands = 0
 
     def close(self):
         if getattr(self, 'h', None):
@@ -384,7 +389,40 @@ class Engine(object):
             setattr(t, k, C.cast(base + 8 * off, c_dp))
             off += n
         self._ck(self.L.nk_step(self.h, int(nsteps), C.byref(t)), 'nk_step')
+        if self.nbands > 0:
+            out['band_F'], out['band_N'], out['band_steps'] = self._band_rows()
         return out
+
+    # ------------------------------------------------------- band-resolved heat flux
+    def set_bands(self, band_of_mode, nbands):
+        """Tally the heat flux per band as well (nk_set_bands): band_of_mode[M] = band of every global mode q*J+j, -1 = none
+        (setup_tables.band_map builds the usual ones).  nbands = 0 turns it off.  Then step() also returns, for the heat-flux
+        steps of the call, band_F [rows, S, nbands, 3], band_N [rows, S, nbands] and band_steps [rows] (absolute steps)."""
+        nbands = int(nbands)
+        bm = None if nbands == 0 else _i(band_of_mode).ravel()
+        if bm is not None and bm.shape[0] != self.M:
+            raise NkError('set_bands: band_of_mode has %d entries, the material %d modes' % (bm.shape[0], self.M))
+        self._ck(self.L.nk_set_bands(self.h, nbands, _p(bm, c_ip)), 'nk_set_bands')
+        self.nbands = nbands
+
+    def _band_rows(self):
+        S, B = self.S, self.nbands
+        n = C.c_int32(0)
+        self._ck(self.L.nk_get_band_rows(self.h, None, None, None, 0, C.byref(n)), 'nk_get_band_rows')
+        r = int(n.value)
+        F, N, st = np.zeros((r, S, B, 3)), np.zeros((r, S, B)), np.zeros(r, dtype=np.int64)
+        if r > 0:
+            self._ck(self.L.nk_get_band_rows(self.h, _p(F), _p(N), st.ctypes.data_as(C.POINTER(C.c_int64)), r, C.byref(n)),
+                     'nk_get_band_rows')
+        return F, N, st
+
+    def tally_bands_state(self):
+        """Band sums of the particles where they stand, after the relaxation, against each particle's interpolated temperature:
+        F [S, nbands, 3], N [S, nbands] (nk_tally_bands_state; all ranks)."""
+        S, B = self.S, self.nbands
+        F, N = np.zeros((S, B, 3)), np.zeros((S, B))
+        self._ck(self.L.nk_tally_bands_state(self.h, _p(F), _p(N)), 'nk_tally_bands_state')
+        return F, N
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

@@ -46,6 +46,8 @@ def main(argv=None):
     print('Saving end of run particle data...')
     pop.write_final_state(geo)
     pop.view.postprocess()
+    if pop.n_bands > 0 and pop.rank == 0:
+        pop.write_k_contribution()
     total = datetime.now() - start
     print('Total time: %s' % total)
     if out is not None:

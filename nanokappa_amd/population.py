@@ -20,8 +20,28 @@ import numpy as np
 
 from .constants import Constants
 from . import setup_tables as ST
+from . import spectral as SP
 from .engine import Engine
 from .sharding import shard_range
+
+
+def spectral_bands_option(value):
+    """--spectral_bands N [frequency|branch] -> (N, kind); N = 0 (or no value) is off.  'branch' alone means one band per
+    branch (for 'branch' any N > 0 turns it on; the count is the material's number of branches)."""
+    v = list(value or [])
+    usage = '--spectral_bands: expected N [frequency|branch] (N >= 0) or branch, got %r' % ' '.join(str(x) for x in v)
+    if not v:
+        return 0, 'frequency'
+    if v == ['branch']:
+        return 1, 'branch'
+    try:
+        n = int(v[0])
+    except ValueError:
+        raise ValueError(usage)
+    kind = v[1] if len(v) > 1 else 'frequency'
+    if n < 0 or len(v) > 2 or kind not in ('frequency', 'branch'):
+        raise ValueError(usage)
+    return n, kind
 
 
 class _Stats(object):
@@ -64,6 +84,12 @@ class _Stats(object):
             weak = np.absolute(self.mean_con_k) < self.std_con_k                          # Visualisation.py:209-212
             self.mean_con_k = np.where(weak, np.nan, self.mean_con_k)
             self.std_con_k = np.where(weak, np.nan, self.std_con_k)
+        # frequency-resolved conductivity per connection [C, B] (--spectral_bands): the rows' band_k over the same window
+        bk = [r['band_k'] for r in rows if r.get('band_k') is not None]
+        if bk:
+            bk = np.array(bk)
+            with np.errstate(invalid='ignore'):
+                self.mean_band_k, self.std_band_k = np.nanmean(bk, axis=0), np.nanstd(bk, axis=0)
 
 
 class Population(Constants):
@@ -157,6 +183,11 @@ class Population(Constants):
             pos, modes, occ = self.initialise_all_particles(geometry, phonon)
 
         self._configure_engine(geometry, phonon)
+        # frequency-resolved conductivity (--spectral_bands N [frequency|branch]; off by default): band sums on the device
+        self.n_bands = 0
+        nb, kind = spectral_bands_option(getattr(args, 'spectral_bands', None))
+        if nb > 0:
+            self.set_bands(kind, nb, phonon)
         if comm is not None:               # nk_comm_init decides what one rank needs (rank / nranks; NK_FORCE_COMM)
             self.engine.comm_init(comm[0], self.rank, self.nranks)
         J = phonon.number_of_branches
@@ -189,6 +220,54 @@ class Population(Constants):
         self._record_convergence(geometry)
         self.view = _Stats(self)
         print('Initialisation done!')
+
+    # ----------------------------------------------------------------------- frequency-resolved conductivity
+    def set_bands(self, kind='frequency', nbands=100, phonon=None):
+        """Tally the heat flux by band from here on: kind 'frequency' (nbands bins of omega, Visualisation.py:609), 'branch',
+        or an array with the band of every global mode q*J+j (-1 = none; e.g. mean-free-path bands).  nbands = 0: off."""
+        phonon = phonon if phonon is not None else self._ph
+        if nbands == 0 and isinstance(kind, str):
+            self.engine.set_bands(None, 0)
+            self.n_bands = 0
+            return
+        self.band_of_mode, self.n_bands, self.band_edges = SP.band_map(phonon.omega, nbands, kind)
+        self.band_kind = kind if isinstance(kind, str) else 'custom'
+        self.engine.set_bands(self.band_of_mode, self.n_bands)
+
+    def _window_T(self):
+        """Mean subvolume temperatures over the last n_mean convergence rows (Visualisation's mean_T)."""
+        rows = self.conv_rows[-self.n_mean:]
+        return np.array([r['T'] for r in rows]).mean(axis=0) if rows else np.asarray(self.subvol_temperature, dtype=float)
+
+    def band_k(self, F, N, T=None, phonon=None, n_sv=None):
+        """k(omega) [C, B] of every subvolume connection from band sums F [S, B, 3], N [S, B] (Visualisation.py:598-637);
+        n_sv: particles per subvolume (the normalisation counts all of them, also those of modes in no band)."""
+        ph = phonon if phonon is not None else self._ph
+        geo = self._geo
+        return SP.connection_k(F, N, geo.subvol_connections, geo.subvol_con_vectors, self._window_T() if T is None else T,
+                               ph.number_of_active_modes, ph.number_of_qpoints * ph.volume_unitcell, self.eVpsa2_in_Wm2,
+                               self.a_in_m, n_sv=n_sv)
+
+    def flux_contribution(self, T=None):
+        """The reference's Visualisation.flux_contribution numbers for the current state (one snapshot, after the relaxation,
+        occupations against each particle's interpolated temperature): dict with the band edges and centres, k [C, B] per
+        connection and its cumulative sum over the bands.  T: the temperatures of dT (default: window means, mean_T there)."""
+        if self.n_bands <= 0:
+            raise RuntimeError('flux_contribution: no bands (--spectral_bands or Population.set_bands)')
+        F, N = self.engine.tally_bands_state()
+        n_sv = self.engine.tally_state()[1]
+        if self.nranks > 1:
+            n_sv = self.engine.comm_allreduce(n_sv)[0]
+        k = self.band_k(F, N, T, n_sv=n_sv)
+        e = self.band_edges
+        return dict(edges=e, centers=(e[:-1] + e[1:]) / 2, k=k, cumulative=np.cumsum(k, axis=1), F=F, N=N)
+
+    def write_k_contribution(self):
+        v = self.view
+        if getattr(v, 'mean_band_k', None) is None or not self.results_folder_name:
+            return None
+        return SP.write_k_contribution(SP.k_contribution_path(self.results_folder_name), self.band_edges, self.band_kind,
+                                       self._geo.subvol_connections, v.mean_band_k, v.std_band_k, self.current_timestep)
 
     # ----------------------------------------------------------------------------------- setup
     def _shard(self, n):
@@ -674,6 +753,9 @@ class Population(Constants):
                         self.res_heat_flux = self.res_heat_flux + t['res_flux'][q]
                     self._bal_steps += s1 - s0
                 if (self.current_timestep % self.n_dt_to_conv) == 0:                # Population.py:1762-1767
+                    if self.n_bands > 0:                        # this step's band row (nk_step tallied it after the sweep)
+                        r = np.nonzero(t['band_steps'] == self.current_timestep - 1)[0]
+                        self._band_row = (t['band_F'][r[0]], t['band_N'][r[0]]) if r.size else None
                     self.subvol_heat_flux = self._normalise_flux(phonon, t['flux_raw'][s], self.subvol_N_p)
                     self.calculate_kappa(geometry)
                     self.adjust_reservoir_balance(geometry, phonon)
@@ -686,6 +768,8 @@ class Population(Constants):
         if self.results_folder_name and getattr(self.args, 'checkpoint', True):     # every rank: its shard of the particles
             self.write_final_state(geometry)
         self.view.postprocess(verbose=False)
+        if self.n_bands > 0 and self.rank == 0:
+            self.write_k_contribution()
         self.update_residue(geometry)
         info = 'Timestep {:>5d} - max residue: {:>9.3e} ({:<9s}) ['.format(int(self.current_timestep), self.max_residue, self.max_residue_qt)
         for sv in range(self.n_of_subvols):
@@ -765,7 +849,13 @@ class Population(Constants):
                    en_res=np.array(self.res_energy_balance), N_p=self.N_p, sv_Np=np.array(self.subvol_N_p),
                    kappa=getattr(self, 'kappa', np.nan), sv_k=np.array(getattr(self, 'subvol_kappa', np.zeros(0))),
                    con_k=np.array(getattr(self, 'svcon_kappa', np.zeros(0))))
+        band = getattr(self, '_band_row', None)
+        if band is not None:
+            self._band_row = None
+            row['band_F'], row['band_N'] = band
         self.conv_rows.append(row)
+        if band is not None:                                    # dT of the window means, this row included
+            row['band_k'] = self.band_k(band[0], band[1], n_sv=row['sv_Np'])
         if len(self.conv_rows) > max(self.n_mean, 1000):
             del self.conv_rows[:-max(self.n_mean, 1000)]
         if self.rank == 0 and self.results_folder_name:
