@@ -2203,12 +2203,11 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     return NK_OK;
 }
 
-// Small ensembles: many steps per launch (k_resident, nk_kernels.h).  OPT-IN (NK_RESIDENT=1): measured SLOWER than the launches
-// it replaces -- 1e5 particles: 0.081 (9^3 x 6 modes) / 0.092 ms (31^3 x 6) per step against 0.032 / 0.037 ms; 1e6: 0.130-0.136
-// against 0.046-0.050 (profiles/r04_notes.txt (9)): a step's device-scope barrier and its FP64 atomics on 111 shared addresses
-// cost more than the two launches and the reduce chain they save.  One rank, no rough facets, tables in LDS, not 'one_to_one', no
-// RBF temperatures, at most NK_RESIDENT_MAX slots (default 1.2e6).  Kept, with its parity tests, as the measured record of
-// that design.
+// Small ensembles: many steps per launch (k_resident, nk_kernels.h).  OPT-IN (NK_RESIDENT=1): at 1e5 particles (31^3 x 6 modes)
+// it measured faster than the launches it replaces -- 0.027 ms per step against 0.034-0.037 -- but at 1e6 slower, 0.057 against
+// 0.048 (profiles/r04_notes.txt (17), (26); its first version, with FP64 atomics on shared addresses and device-scope fences,
+// was slower at every size, (9)).  One rank, no rough facets, tables in LDS, not 'one_to_one', no RBF temperatures, at most
+// NK_RESIDENT_MAX slots (default 1.2e6).
 static inline bool nk_want_resident(const nk_ctx *ctx) {
     const NkDev &d = ctx->d;
     if (!getenv("NK_RESIDENT") || getenv("NK_NO_RESIDENT") || ctx->comm || d.nranks != 1 || d.Fr > 0 || d.mig_buf || d.qx || nk_geom_mode(ctx) != 1) return false;
@@ -2258,6 +2257,8 @@ static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h,
     int G = std::min(ctx->num_cu * per_cu, (d.nseg + NK_WG / 64 - 1) / (NK_WG / 64));
     if (const char *e = getenv("NK_RESIDENT_GRID")) { const int v = atoi(e); if (v >= 1 && v < G) G = v; }   // developer probe
     G = std::max(1, G);
+    // the tally rows, double-buffered by step parity (k_resident), live in `partials`: num_cu * 16 * NB doubles >= 2 G NBP, G <= 2 num_cu
+    NK_ARG((size_t)2 * G * (size_t)((NB + 1) & ~1) <= (size_t)ctx->num_cu * 16 * NB, "nk_step_resident: tally rows exceed the partials buffer");
     if (ctx->evpool.empty()) { ctx->evpool.resize(16 * 4 + 2); for (auto &e : ctx->evpool) NK_HIP(hipEventCreate(&e)); }
     hipEvent_t t0 = ctx->evpool[64], t1 = ctx->evpool[65];
     const bool relax0 = ctx->pending_relax;

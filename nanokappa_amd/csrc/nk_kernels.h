@@ -1690,6 +1690,12 @@ __global__ __launch_bounds__(NK_WG) void k_tail(NkDev d, uint32_t step_next, int
 // occupancy query allows.  A wait that is not met within ~2 s gives up (overflow bit 256) instead of hanging the device.
 // bar[1]: this launch's update asked for a halt; bar[32 + g]: steps of this launch whose row workgroup g has written; bar[1056 + t]:
 // steps of this launch whose temperature of subvolume t is published.  Zeroed by the host before every launch.
+// The tally rows are double-buffered by the step's parity (rows + ((s & 1) * G + wg) * NBP): the only wait between a workgroup's
+// row store of step s and its row store of step s + 1 is on the S temperature flags, and owners of the other columns (flux,
+// N_leaving, reservoir tallies, N_emitted) may still be reading step s's rows then.  With two buffers, a workgroup's store of
+// step s + 2's row into the buffer of step s comes after it saw every temperature flag of step s + 1; each of those was raised
+// after its owner saw every workgroup's row flag of step s + 1; and each workgroup raised that flag after its own reads of step s's
+// rows had returned (program order: their values went into its step-s sums).  So no row is overwritten while it is read.
 __device__ __forceinline__ bool nk_wait_word(const unsigned int *w, unsigned int atleast) {
     int spins = 0;
     while (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < atleast) {
@@ -1732,7 +1738,8 @@ __global__ __launch_bounds__(NK_WG, 2) void k_resident(NkDev d, uint32_t step0, 
 #else
         nk_sweep_body<1, false, false, PID, false, LREC, 0, BOX>(d, L, step, s == 0 ? relax0 : 1, do_flux, wg, G);
 #endif
-        // ---- this workgroup's tally sums (the row of nk_lds_flush), then its flag
+        // ---- this workgroup's tally sums (the row of nk_lds_flush) into this step's buffer of rows, then its flag
+        unsigned long long *rows_s = rows + (size_t)(s & 1) * G * NBP;
         __syncthreads();
         if (mark) mk[1] = __builtin_amdgcn_s_memrealtime();
         for (int b = tid; b < NB; b += NK_WG) {
@@ -1744,9 +1751,9 @@ __global__ __launch_bounds__(NK_WG, 2) void k_resident(NkDev d, uint32_t step0, 
             else if (b < 5 * S + 2 * R) v = L.bins.resb[4 * (b - 5 * S - R)];
             else if (b < 5 * S + 5 * R) { const int k = b - 5 * S - 2 * R; v = L.bins.resb[4 * (k / 3) + 1 + (k % 3)]; }
             else v = (double)L.bins.misc[0];
-            __hip_atomic_store(rows + (size_t)wg * NBP + b, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(rows_s + (size_t)wg * NBP + b, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (tid == 0 && NBP > NB) __hip_atomic_store(rows + (size_t)wg * NBP + NB, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0 && NBP > NB) __hip_atomic_store(rows_s + (size_t)wg * NBP + NB, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // the row's stores have completed (no cache is written back)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
@@ -1787,8 +1794,8 @@ __global__ __launch_bounds__(NK_WG, 2) void k_resident(NkDev d, uint32_t step0, 
                 const int c0 = k < S ? k : 2 * S + (k - S), c1 = k < S ? S + k : -1;
                 double v0 = 0.0, v1 = 0.0;
                 for (int g = tid; g < G; g += NK_WG) {
-                    v0 += __longlong_as_double((long long)__hip_atomic_load(rows + (size_t)g * NBP + c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    if (c1 >= 0) v1 += __longlong_as_double((long long)__hip_atomic_load(rows + (size_t)g * NBP + c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                    v0 += __longlong_as_double((long long)__hip_atomic_load(rows_s + (size_t)g * NBP + c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                    if (c1 >= 0) v1 += __longlong_as_double((long long)__hip_atomic_load(rows_s + (size_t)g * NBP + c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                 }
                 // the workgroup's sum in a fixed order: a tree over the thread index
                 double *red = L.colsum;

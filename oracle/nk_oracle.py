@@ -121,6 +121,7 @@ def make_material(tables):
     m.hbar, m.kb, m.QV = float(tables['hbar']), float(tables['kb']), float(tables['QV'])
     m.active_modes = int(tables['active_modes'])
     _keep(m, om, vg, tg, lt, ta, ea)
+    m.group_vel_array = vg
     return m
 
 
@@ -314,6 +315,9 @@ class OracleSim(object):
         self.res_energy = np.zeros(max(self.R, 1))
         self.res_flux = np.zeros((max(self.R, 1), 3))
         self.flux = np.zeros((self.S, 3))
+        self.N_emitted = 0                 # particles nko_emit created at the last step
+        self.res_energy_step = np.zeros(max(self.R, 1))       # the last step's share of res_energy / res_flux
+        self.res_flux_step = np.zeros((max(self.R, 1), 3))
         self.step = 0
         self.rank, self.nranks = 0, 1
 
@@ -324,6 +328,28 @@ class OracleSim(object):
         bad = self.L.nko_init_boundaries(self.ref(self.mesh), self.ref(self.mat), self.ref(self.p), self.ref(self.P.s))
         if self.p.box and bad > 0:        # particles outside the box with a wall ahead: the engine goes back to cached hits
             self.p.box = 0
+
+    def _emit(self, emit):
+        self.N_emitted = 0
+        if emit and self.R > 0:
+            n = self.L.nko_emit(self.ref(self.mat), self.ref(self.mesh), self.ref(self.res), self.ref(self.p),
+                                C.c_int64(self.step), C.c_int32(self.rank), C.c_int32(self.nranks), self.ref(self.P.s))
+            if n < 0:
+                raise RuntimeError('oracle particle capacity exceeded')
+            self.N_emitted = int(n)
+
+    def _boundary_scattering(self):
+        """nko_boundary_scattering adds to the reservoir tallies it is given: it tallies the step into zeroed arrays (the step's own
+        share, as the engine's rows hold it; a difference of the running sums would lose digits to them over a long run), which
+        are then added to the running sums res_energy / res_flux."""
+        self.res_energy_step = np.zeros_like(self.res_energy)
+        self.res_flux_step = np.zeros_like(self.res_flux)
+        self.L.nko_boundary_scattering(self.ref(self.mat), self.ref(self.mesh), self.ref(self.sv), self.ref(self.res),
+                                       self.ref(self.rough), self.ref(self.p), _p(self.T_sv, c_dp), C.c_int64(self.step),
+                                       self.ref(self.P.s), _p(self.N_leaving, c_lp), _p(self.res_energy_step, c_dp),
+                                       _p(self.res_flux_step, c_dp))
+        self.res_energy += self.res_energy_step
+        self.res_flux += self.res_flux_step
 
     def run_timestep_sharded(self, allreduce, emit=True, contains_every=100, halt_requests=(0, 0)):
         """run_timestep for one rank of a particle-sharded ensemble: `allreduce(vec)` sums a float64 vector over the
@@ -336,15 +362,8 @@ class OracleSim(object):
             L.nko_contains_check(self.ref(self.mat), self.ref(self.mesh), self.ref(self.p),
                                  C.c_int64(self.step), self.ref(self.P.s))
         L.nko_drift(self.ref(self.mat), self.ref(self.p), self.ref(self.P.s))
-        if emit and self.R > 0:
-            n = L.nko_emit(self.ref(self.mat), self.ref(self.mesh), self.ref(self.res), self.ref(self.p),
-                           C.c_int64(self.step), C.c_int32(self.rank), C.c_int32(self.nranks), self.ref(self.P.s))
-            if n < 0:
-                raise RuntimeError('oracle particle capacity exceeded')
-        L.nko_boundary_scattering(self.ref(self.mat), self.ref(self.mesh), self.ref(self.sv), self.ref(self.res),
-                                  self.ref(self.rough), self.ref(self.p), _p(self.T_sv, c_dp), C.c_int64(self.step),
-                                  self.ref(self.P.s), _p(self.N_leaving, c_lp), _p(self.res_energy, c_dp),
-                                  _p(self.res_flux, c_dp))
+        self._emit(emit)
+        self._boundary_scattering()
         L.nko_tally(self.ref(self.mat), self.ref(self.sv), self.ref(self.p), self.ref(self.P.s), _p(self.T_sv, c_dp),
                     _p(self.N_sv, c_lp), _p(self.E_raw, c_dp))
         vec = np.concatenate((self.E_raw, self.N_sv.astype(np.float64), self.N_leaving[:self.R].astype(np.float64),
@@ -368,15 +387,8 @@ class OracleSim(object):
             L.nko_contains_check(self.ref(self.mat), self.ref(self.mesh), self.ref(self.p),
                                  C.c_int64(self.step), self.ref(self.P.s))
         L.nko_drift(self.ref(self.mat), self.ref(self.p), self.ref(self.P.s))
-        if emit and self.R > 0:
-            n = L.nko_emit(self.ref(self.mat), self.ref(self.mesh), self.ref(self.res), self.ref(self.p),
-                           C.c_int64(self.step), C.c_int32(self.rank), C.c_int32(self.nranks), self.ref(self.P.s))
-            if n < 0:
-                raise RuntimeError('oracle particle capacity exceeded')
-        L.nko_boundary_scattering(self.ref(self.mat), self.ref(self.mesh), self.ref(self.sv), self.ref(self.res),
-                                  self.ref(self.rough), self.ref(self.p), _p(self.T_sv, c_dp), C.c_int64(self.step),
-                                  self.ref(self.P.s), _p(self.N_leaving, c_lp), _p(self.res_energy, c_dp),
-                                  _p(self.res_flux, c_dp))
+        self._emit(emit)
+        self._boundary_scattering()
         if self.R > 0 and self.res.gen == 2:             # one_to_one: next step emits what left now (Population.py:1749)
             self.res.n_leaving_array[:] = self.N_leaving[:self.R]
         L.nko_refresh_temperatures(self.ref(self.mat), self.ref(self.sv), self.ref(self.p), self.ref(self.P.s),

@@ -6,7 +6,7 @@ import sys
 import numpy as np
 import pytest
 
-from util import golden, sub, golden_phonon, rel_err, case_tables, random_population, make_oracle_sim, make_engine, allclose, same_event_rule, TOL_T, TOL_X, TOL_X_LONG, TOL_NTS, TOL_OCC, TOL_OCC_GRID, TOL_E, TOL_RES
+from util import golden, sub, golden_phonon, rel_err, case_tables, random_population, make_oracle_sim, make_engine, allclose, same_event_rule, TOL_T, TOL_X, TOL_X_LONG, TOL_NTS, TOL_OCC, TOL_OCC_GRID, TOL_E, TOL_RES, oracle_row, assert_rows, assert_runs_equal, TOL_E_GRID, TOL_ROW_ERAW_LONG, TOL_ROW_FLUX_GRID, TOL_ROW_RES_GRID
 
 pytestmark = pytest.mark.gpu
 
@@ -221,8 +221,8 @@ def test_multistep_vs_oracle(case, store, monkeypatch):
     per-step tallies and the final particle set (matched by particle id).  Both layouts of the particle store: the box store
     (no cached next hit; these meshes are axis-aligned boxes) and, with NK_NO_BOX, the cached one that every other mesh uses.
     And the other way of stepping a small ensemble, NK_RESIDENT=1: many steps per launch with a grid barrier per step
-    (k_resident; 'ttp' only -- rough facets keep the launch-per-step path).  It is opt-in because it measured slower; its
-    results are the same."""
+    (k_resident; 'ttp' only -- rough facets keep the launch-per-step path).  It is opt-in: faster than the launches at 1e5
+    particles, slower at 1e6 (profiles/r04_notes.txt (26)); its results are the same."""
     if store.startswith('cached'):
         monkeypatch.setenv('NK_NO_BOX', '1')
     if store.endswith('resident'):
@@ -239,10 +239,7 @@ def test_multistep_vs_oracle(case, store, monkeypatch):
     assert eng.timing()['emit_fused'] == (2 if store.endswith('resident') else 1)   # which path ran (1: the emission rides in the tail launch)
     for s in range(nsteps):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert np.array_equal(t['N_leaving'][s], sim.N_leaving[:2]), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
-        assert rel_err(t['E_sv'][s], sim.E_sv) < TOL_E
+        assert_rows(t, s, oracle_row(sim))
     p = eng.download()
     n = sim.P.N
     assert p['pid'].shape[0] == n
@@ -272,9 +269,7 @@ def test_multistep_other_generators(gen):
     for s in range(nsteps):
         n_before = sim.P.N
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert np.array_equal(t['N_leaving'][s], sim.N_leaving[:2]), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim))
         if gen == 2 and s > 0:
             assert t['N_emitted'][s] == t['N_leaving'][s - 1].sum()
     p = eng.download()
@@ -328,8 +323,7 @@ def test_other_geometries_vs_oracle(name):
     t = eng.step(nsteps)
     for s in range(nsteps):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim))
     p = eng.download()
     n = sim.P.N
     assert p['pid'].shape[0] == n
@@ -368,8 +362,7 @@ def test_grid_subvolumes_vs_oracle(interp):
     t = eng.step(nsteps)
     for s in range(nsteps):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim))
     p = eng.download()
     n = sim.P.N
     o1, o2 = np.argsort(p['pid']), np.argsort(sim.P.pid[:n])
@@ -396,8 +389,8 @@ def test_rough_wire_grid_subvolumes_vs_oracle(sides, interp):
     t = eng.step(nsteps)
     for s in range(nsteps):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim), tol_E=TOL_E_GRID, tol_raw=TOL_ROW_ERAW_LONG, tol_flux=TOL_ROW_FLUX_GRID,
+                    tol_res=TOL_ROW_RES_GRID)
     p = eng.download()
     n = sim.P.N
     o1, o2 = np.argsort(p['pid']), np.argsort(sim.P.pid[:n])
@@ -571,8 +564,7 @@ def test_k_reflection_model_vs_oracle():
     t = eng.step(nsteps)
     for s in range(nsteps):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim))
     p = eng.download()
     n = sim.P.N
     o1, o2 = np.argsort(p['pid']), np.argsort(sim.P.pid[:n])
@@ -595,6 +587,7 @@ def test_rccl_path_single_rank(monkeypatch):
     t1 = eng.step(6)
     assert np.array_equal(t0['N_sv'], t1['N_sv'])
     assert allclose(t0['T_sv'], t1['T_sv'], rtol=0, atol=TOL_T)     # (the two runs sum their tally rows in different orders)
+    assert_runs_equal(t0, t1)      # all nine tallies of every step: the all-reduced vector and what the update made of it
 
 
 @pytest.mark.parametrize('case', ['ttp', 'ttrrp', 'wire72'])

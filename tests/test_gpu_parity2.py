@@ -9,7 +9,7 @@ import tempfile
 import numpy as np
 import pytest
 
-from util import rel_err, case_tables, random_population, make_oracle_sim, make_engine, allclose, same_event_rule, TOL_T, TOL_X, TOL_X_LONG, TOL_NTS, TOL_OCC
+from util import rel_err, case_tables, random_population, make_oracle_sim, make_engine, allclose, same_event_rule, TOL_T, TOL_X, TOL_X_LONG, TOL_NTS, TOL_OCC, oracle_row, assert_rows, assert_runs_equal, engine_row, RUN_TOL, TOL_ROW_ERAW_LONG
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
@@ -48,8 +48,7 @@ def steps_agree(eng, sim, nsteps, chunk=50):
         t = eng.step(k)
         for s in range(k):
             sim.run_timestep()
-            assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % (done + s)
-            assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % (done + s)
+            assert_rows(t, s, oracle_row(sim), label=done + s, tol_raw=TOL_ROW_ERAW_LONG)
         done += k
 
 
@@ -179,8 +178,7 @@ def test_other_generators_on_a_large_mesh(gen):
     t = eng.step(nsteps)
     for s in range(nsteps):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim))
         if gen == 2 and s > 0:
             assert t['N_emitted'][s] == t['N_leaving'][s - 1].sum()
     assert t['N_emitted'].sum() > 0
@@ -322,8 +320,7 @@ def test_engine_from_a_file_loaded_material_vs_oracle_on_reference_tables(tmp_pa
     t = eng.step(25)
     for s in range(25):
         sim.run_timestep()
-        assert np.array_equal(t['N_sv'][s], sim.N_sv), 'step %d' % s
-        assert allclose(t['T_sv'][s], sim.T_sv, rtol=0, atol=TOL_T), 'step %d' % s
+        assert_rows(t, s, oracle_row(sim, flux_every=pop.n_dt_to_conv))
     assert t['N_emitted'].sum() > 0 and t['N_leaving'].sum() > 0
     compare_by_state(eng.download(), sim)
 
@@ -350,6 +347,7 @@ def test_stepping_one_by_one_equals_one_call():
         assert np.array_equal(ta[k], np.concatenate([r[k] for r in rows])), k
     # (not bit for bit: the stand-alone relaxation of the download and the re-dealt tiles after the regrow round differently)
     assert allclose(ta['T_sv'], np.concatenate([r['T_sv'] for r in rows]), rtol=0, atol=TOL_T)
+    assert_runs_equal(ta, {k: np.concatenate([r[k] for r in rows]) for k in ta})      # all nine tallies, step by step
     pa, pb = a.download(), b.download()
     oa, ob = np.argsort(pa['pid']), np.argsort(pb['pid'])
     assert np.array_equal(pa['pid'][oa], pb['pid'][ob])
@@ -385,6 +383,7 @@ def test_alternating_walk_equals_walking_upwards_only(monkeypatch, store):
     for k in ('N_sv', 'N_emitted', 'N_leaving'):
         assert np.array_equal(tb[k], np.concatenate([r[k] for r in rows])), k
     assert allclose(tb['T_sv'], np.concatenate([r['T_sv'] for r in rows]), rtol=0, atol=TOL_T)
+    assert_runs_equal(tb, {k: np.concatenate([r[k] for r in rows]) for k in tb})
     pa, pb = a.download(), b.download()
     oa, ob = np.argsort(pa['pid']), np.argsort(pb['pid'])
     assert np.array_equal(pa['pid'][oa], pb['pid'][ob]) and np.array_equal(pa['mode'][oa], pb['mode'][ob])
@@ -399,3 +398,67 @@ def test_alternating_walk_equals_walking_upwards_only(monkeypatch, store):
     b.init_boundaries()
     t2b = b.step(12)
     assert np.array_equal(t2a['N_sv'], t2b['N_sv']) and allclose(t2a['T_sv'], t2b['T_sv'], rtol=0, atol=TOL_T)
+
+
+@pytest.mark.parametrize('grid', [0, 7])
+@pytest.mark.parametrize('store', ['box', 'cached'])
+def test_resident_long_run_every_row(store, grid, monkeypatch):
+    """The resident kernel (NK_RESIDENT=1, k_resident) at config 1's own size, 250 steps in calls of 37, 100 and 113 (relaunches
+    at the contains_check steps 100 and 200, 25 heat-flux steps): every row against the oracle and against the launch path on
+    the same seed.  grid 7 (NK_RESIDENT_GRID): few workgroups, each owning temperature columns as well as flux, reservoir and
+    emission columns of the tally rows."""
+    if store == 'cached':
+        monkeypatch.setenv('NK_NO_BOX', '1')
+    if grid:
+        monkeypatch.setenv('NK_RESIDENT_GRID', str(grid))
+    ct = case_tables('ttp')
+    pos, mode, occ, counter = random_population(ct, 100000, seed=13)
+    sim = make_oracle_sim(ct, pos, mode, occ, counter, seed=61)
+    res = make_engine(ct, pos, mode, occ, counter, seed=61)
+    ref = make_engine(ct, pos, mode, occ, counter, seed=61)
+    assert same_event_rule(res, sim) == (1 if store == 'box' else 0)
+    done = 0
+    for n in (37, 100, 113):
+        monkeypatch.setenv('NK_RESIDENT', '1')
+        t = res.step(n)
+        assert res.timing()['emit_fused'] == 2                 # the resident kernel ran
+        monkeypatch.delenv('NK_RESIDENT')
+        tr = ref.step(n)
+        assert ref.timing()['emit_fused'] == 1
+        for s in range(n):
+            sim.run_timestep()
+            assert_rows(t, s, oracle_row(sim), label=done + s)
+            assert_rows(t, s, engine_row(tr, s), label=done + s, **RUN_TOL)
+        done += n
+    assert done == 250
+    compare_by_pid(res.download(), sim, pos_atol=TOL_X_LONG)
+
+
+@pytest.mark.parametrize('case', ['ttp', 'ttrrp'])
+def test_box_store_against_the_references_event_rule(case):
+    """The box store (events read off the position) against the oracle on the reference's own rule (the cached n_timesteps,
+    decremented every step: Population.py:795, :1551), 130 steps across the contains_check at step 100: the same events, so
+    identical counts and particle sets; positions and n_timesteps to the rounding of the drift, which the two rules do
+    differently."""
+    ct = case_tables(case)
+    pos, mode, occ, counter = random_population(ct, 30000, seed=17)
+    sim = make_oracle_sim(ct, pos, mode, occ, counter, seed=99, box=False)
+    eng = make_engine(ct, pos, mode, occ, counter, seed=99)
+    assert eng.timing()['box_store'] == 1 and sim.p.box == 0
+    done = 0
+    for n in (65, 65):
+        t = eng.step(n)
+        for s in range(n):
+            sim.run_timestep()
+            assert_rows(t, s, oracle_row(sim), label=done + s)
+        done += n
+    p = eng.download()
+    n = sim.P.N
+    assert p['pid'].shape[0] == n
+    o1, o2 = np.argsort(p['pid']), np.argsort(sim.P.pid[:n])
+    assert np.array_equal(p['pid'][o1], sim.P.pid[:n][o2])
+    assert np.array_equal(p['mode'][o1], sim.P.mode[:n][o2])
+    assert np.array_equal(p['facet'][o1], sim.P.facet[:n][o2])
+    assert allclose(p['positions'][o1], sim.P.pos[:n][o2], rtol=0, atol=TOL_X_LONG)
+    assert allclose(p['n_timesteps'][o1], sim.P.n_ts[:n][o2], rtol=0, atol=TOL_X_LONG)
+    assert rel_err(p['occupation'][o1], sim.P.occ[:n][o2]) < TOL_OCC

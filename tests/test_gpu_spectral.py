@@ -18,6 +18,11 @@ TOL_BAND_F = 5e-13
 # k(omega) of state mode against the reference's own flux_contribution, relative to the largest |k|: the engine's per-particle
 # temperatures and occupations against the reference's, summed by band; 10x the deviation measured on the MI355X (1.5e-14)
 TOL_K_GOLDEN = 2e-13
+# With tiles of bands and modes in no band, relative to the largest |value| of the row: the sum over the bands against flux_raw less
+# the particles in no band, and flux_raw against the oracle's particles; 10x the deviation measured on the MI355X (1.5e-14, 1.6e-14)
+TOL_BAND_SUM = 1.5e-13
+# ... the state mode against the host formula (measured 1.6e-16)
+TOL_BAND_STATE = 1.5e-15
 
 
 def band_table(ct, nbands, kind):
@@ -248,3 +253,104 @@ def test_state_mode_against_reference_golden():
     print('state mode against the reference golden: largest deviation %.3e of max |k|' % d)
     assert d <= TOL_K_GOLDEN
     assert np.allclose(fc['cumulative'], np.cumsum(y, axis=1), rtol=0, atol=10 * TOL_K_GOLDEN * np.max(np.abs(y)) * y.shape[1])
+
+
+# ---- band tables wider than one LDS tile (nk_band_tile / nk_band_pass: passes of Bt bands, k_spectral_reduce writing tile b0 at
+# band offset b0) and modes in no band (-1: k_spectral's skip of b outside the tile)
+# The upper bound of a tile, whatever else the kernels keep in LDS: nk_band_tile gives S x Bt bins of 28 B at most 64 KB.
+def max_tile(S):
+    return 65536 // (28 * S)
+
+
+def holey_table(ct, nbands, kind, holes, seed):
+    """kind 'frequency': band_map's bins of omega; 'permuted': band of mode m = perm(m) mod B, so that neighbouring modes fall in
+    different tiles.  holes: about a third of the modes (drawn at random) in no band."""
+    rng = np.random.default_rng(seed)
+    M = ct['ph'].omega.size
+    if kind == 'frequency':
+        band, B = band_table(ct, nbands, kind)
+    else:
+        band, B = (rng.permutation(M) % nbands).astype(np.int32), nbands
+    band = np.array(band, dtype=np.int32)
+    if holes:
+        band[rng.random(M) < 1.0 / 3.0] = -1
+    return band, B
+
+
+def slice100_case():
+    from util import case_from_args
+    argv = ['--geometry', 'box', '--dimensions', '2000', '200', '200', '--subvolumes', 'slice', '100', '0',
+            '--bound_pos', 'relative', '0', '.5', '.5', '1', '.5', '.5', '--bound_cond', 'T', 'T', 'P',
+            '--connect_pos', 'relative', '.5', '0', '.5', '.5', '1', '.5', '.5', '.5', '0', '.5', '.5', '1',
+            '--bound_values', '302', '298', '--poscar_file', 'POSCAR', '--hdf_file', 'synthetic', '--temp_interp', 'linear',
+            '--timestep', '1', '--energy_normal', 'mean', '--particles', 'total', '20000']
+    return case_from_args(argv, 'Si')
+
+
+@pytest.mark.parametrize('case,nbands,kind,holes', [('ttp', 250, 'frequency', False), ('ttp', 1000, 'permuted', True),
+                                                    ('ttrrp', 250, 'permuted', True), ('slice100', 100, 'frequency', True)])
+def test_band_tiles_against_oracle(case, nbands, kind, holes):
+    """Several tiles of bands with a partial last one, bands dealt by a random permutation, a third of the modes in no band,
+    and a film of 100 slices (a tile of a few bands): per band and step against the oracle's particles; the sum over the bands
+    is the subvolume's count and flux less the particles in no band."""
+    from util import rel_row, population_in_mesh, oracle_flux
+    if case == 'slice100':
+        ct = slice100_case()
+        pos, mode, occ, counter = population_in_mesh(ct, 20000, seed=5)
+    else:
+        ct = case_tables(case)
+        pos, mode, occ, counter = random_population(ct, 20000, seed=5)
+    S = ct['centers'].shape[0]
+    band, B = holey_table(ct, nbands, kind, holes, seed=nbands)
+    assert B > max_tile(S)              # two tiles at least (b0 > 0) whatever else the kernels keep in LDS
+    assert (band < 0).any() == holes
+    sim = make_oracle_sim(ct, pos, mode, occ, counter, seed=3)
+    eng = make_engine(ct, pos, mode, occ, counter, seed=3)
+    same_event_rule(eng, sim)
+    eng.set_bands(band, B)
+    t = eng.step(20)
+    assert list(t['band_steps']) == [9, 19]
+    vg = np.asarray(ct['tables']['group_vel']).reshape(-1, 3)
+    for s in range(20):
+        sim.run_timestep()
+        if (s + 1) % 10:
+            continue
+        r = list(t['band_steps']).index(s)
+        F0, N0 = oracle_bands(sim, ct, band, B)
+        assert np.array_equal(t['band_N'][r], N0), 'band counts differ at step %d' % s
+        assert rel_row(t['band_F'][r], F0, tag='band_F', bound=TOL_BAND_F) <= TOL_BAND_F, 'band flux differs at step %d' % s
+        # the particles in no band, from the oracle's: what the sums over the bands leave out
+        n = sim.P.N
+        out = band[sim.P.mode[:n]] < 0
+        N_out = np.bincount(sim.P.sv[:n][out], minlength=S)
+        F_out = np.zeros((S, 3))
+        e = sim.P.energy[:n][out]
+        v = vg[sim.P.mode[:n][out]]
+        for d in range(3):
+            np.add.at(F_out[:, d], sim.P.sv[:n][out], v[:, d] * e)
+        assert np.array_equal(t['band_N'][r].sum(axis=1), t['N_sv'][s] - N_out)
+        assert rel_row(t['band_F'][r].sum(axis=1), t['flux_raw'][s] - F_out, tag='band sum', bound=TOL_BAND_SUM) <= TOL_BAND_SUM
+        assert rel_row(t['flux_raw'][s], oracle_flux(sim), tag='flux_raw', bound=TOL_BAND_SUM) <= TOL_BAND_SUM
+    # the state mode on the same table against the host formula of test_state_mode_against_host
+    F, N = eng.tally_bands_state()
+    F0, N0 = state_on_host(eng, ct, band, B)
+    assert np.array_equal(N, N0)
+    assert rel_row(F, F0, tag='state band_F', bound=TOL_BAND_STATE) <= TOL_BAND_STATE
+
+
+def state_on_host(eng, ct, band, B):
+    p = eng.download()
+    x, m, n = p['positions'], p['mode'].astype(int), p['occupation']
+    S = ct['centers'].shape[0]
+    sv = eng.classify(x)
+    T = eng.eval('interp_T', x)
+    om = ct['ph'].omega.ravel()[m]
+    n0 = np.where(T > 0, eng.eval('occupation', T, m), 0.0)
+    e = ct['ph'].hbar * om * (n - n0)
+    v = np.asarray(ct['tables']['group_vel']).reshape(-1, 3)[m]
+    keep = band[m] >= 0
+    F0, N0 = np.zeros((S, B, 3)), np.zeros((S, B))
+    for d in range(3):
+        np.add.at(F0[:, :, d], (sv[keep], band[m][keep]), v[keep, d] * e[keep])
+    np.add.at(N0, (sv[keep], band[m][keep]), 1.0)
+    return F0, N0

@@ -60,11 +60,26 @@ TOL_OCC = 2e-14       # relative: occupations (measured <= 2.5e-15)
 TOL_OCC_GRID = 1e-12  # ... with grid subvolumes / RBF temperatures (measured 1.2e-14, 8.7e-14)
 TOL_E = 2e-15         # relative: subvolume energies (measured 1.9e-16)
 TOL_RES = 4e-13       # relative: reservoir energy balance, a sum of few terms of either sign (measured 3.5e-14)
+TOL_E_GRID = 5e-14    # ... on the rough wires with grid subvolumes (measured 5.2e-15)
+# The rest of a step's tally row (assert_rows), against the oracle: sums of terms of either sign, relative to the row's largest
+# |value| (profiles/r05_parity_margins.txt).  E_raw's terms nearly cancel (energies against each subvolume's own temperature).
+TOL_ROW_ERAW = 2.5e-11     # E_raw[S] (measured 4.1e-13 ... 2.7e-12)
+TOL_ROW_ERAW_LONG = 1.5e-10  # ... over 260 steps / on the faceted meshes / rough wires with grid subvolumes (measured 1.1e-11, 1.5e-11)
+TOL_ROW_FLUX = 4e-13       # flux_raw[S, 3] (measured 4.4e-15 ... 4.4e-14)
+TOL_ROW_FLUX_GRID = 5e-12  # ... on the rough wires with grid subvolumes (measured 5.9e-13)
+TOL_ROW_RES = 4e-13        # res_energy[R], res_flux[R, 3] of the step (measured 3.8e-15 ... 4.4e-14)
+TOL_ROW_RES_GRID = 5e-12   # ... on the rough wires with grid subvolumes (measured 9.4e-13)
+# Two engine runs of the same steps that sum their tally rows in different orders (assert_runs_equal, resident against launches)
+TOL_RUN_ERAW = 1.2e-11     # (measured 1.2e-12)
+TOL_RUN_FLUX = 3e-14       # (measured 3.4e-15)
+TOL_RUN_RES = 2.5e-14      # (measured 2.7e-15)
 
 
-def _record(kind, value, bound, depth=2):
+def _record(kind, value, bound, depth=2, tag=None):
     f = sys._getframe(depth)
     key = '%s:%d' % (os.path.basename(f.f_code.co_filename), f.f_lineno)
+    if tag:
+        key += ' ' + tag
     test = os.environ.get('PYTEST_CURRENT_TEST', '').split(' ')[0].split('::')[-1]
     m = MARGINS.setdefault(key, dict(kind=kind, worst=0.0, bound=bound, calls=0, tests=set()))
     m['worst'] = max(m['worst'], float(value))
@@ -73,7 +88,8 @@ def _record(kind, value, bound, depth=2):
     m['tests'].add(test)
 
 
-def rel_err(a, b):
+def rel_err(a, b, depth=1, tag=None, bound=None):
+    """max |a - b| / |b|, recorded at the call site `depth` frames up (1: the caller)."""
     a = np.asarray(a, dtype=float)
     b = np.asarray(b, dtype=float)
     scale = np.maximum(np.abs(b), 1e-300)
@@ -81,11 +97,11 @@ def rel_err(a, b):
         e = np.abs(a - b) / scale
     e = np.where((a == b) | (np.isnan(a) & np.isnan(b)), 0.0, e)
     r = float(np.nanmax(e)) if e.size else 0.0
-    _record('rel', r, None)
+    _record('rel', r, None if bound is None else 'rel %g' % bound, depth=depth + 1, tag=tag)
     return r
 
 
-def allclose(a, b, rtol=0.0, atol=0.0):
+def allclose(a, b, rtol=0.0, atol=0.0, depth=1, tag=None):
     """np.allclose with the same meaning (|a - b| <= atol + rtol |b|), recording the largest excess ratio
     |a - b| / (atol + rtol |b|) and the largest absolute deviation at this call site."""
     a = np.asarray(a, dtype=float)
@@ -94,8 +110,21 @@ def allclose(a, b, rtol=0.0, atol=0.0):
         dev = np.abs(a - b)
     dev = np.where((a == b) | (np.isnan(a) & np.isnan(b)), 0.0, dev)
     worst = float(np.nanmax(dev)) if dev.size else 0.0
-    _record('abs', worst, 'rtol %g atol %g' % (rtol, atol))
+    _record('abs', worst, 'rtol %g atol %g' % (rtol, atol), depth=depth + 1, tag=tag)
     return bool(np.allclose(a, b, rtol=rtol, atol=atol, equal_nan=True))
+
+
+def rel_row(a, b, tag=None, bound=None, depth=1):
+    """max |a - b| / max |b|: the deviation relative to the largest |value| of the row (for sums whose terms cancel), recorded
+    like rel_err."""
+    a = np.asarray(a, dtype=float)
+    b = np.asarray(b, dtype=float)
+    with np.errstate(invalid='ignore'):
+        dev = np.abs(a - b)
+    dev = np.where((a == b) | (np.isnan(a) & np.isnan(b)), 0.0, dev)
+    r = float(np.max(dev) / max(np.nanmax(np.abs(b)), 1e-300)) if dev.size else 0.0
+    _record('row', r, None if bound is None else 'row %g' % bound, depth=depth + 1, tag=tag)
+    return r
 
 
 def write_margins(path):
@@ -104,10 +133,10 @@ def write_margins(path):
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, 'w') as f:
         f.write('# largest deviation seen at each comparison of reals in this `pytest -m gpu` run (tests/util.py)\n')
-        f.write('# site | kind (rel = max |a-b|/|b|, abs = max |a-b|) | worst | bound in the test | calls | tests\n')
+        f.write('# site | kind (rel = max |a-b|/|b|, abs = max |a-b|, row = max |a-b| / max |b|) | worst | bound in the test | calls | tests\n')
         for k in sorted(MARGINS):
             m = MARGINS[k]
-            f.write('%-32s %-4s %-12.3e %-24s %5d  %s\n' % (k, m['kind'], m['worst'], m['bound'] or '(see the test)', m['calls'],
+            f.write('%-44s %-4s %-12.3e %-24s %5d  %s\n' % (k, m['kind'], m['worst'], m['bound'] or '(see the test)', m['calls'],
                                                           ','.join(sorted(m['tests']))[:160]))
 
 
@@ -185,6 +214,71 @@ def same_event_rule(eng, sim):
     nk_timing.box_store; oracle: nko_params.box)."""
     assert int(eng.timing()['box_store']) == int(sim.p.box), 'engine box_store %d, oracle box rule %d' % (eng.timing()['box_store'], sim.p.box)
     return int(sim.p.box)
+
+
+# ---------------------------------------------------------------------------------------------------
+# One step's tallies, as a row of Engine.step, from the oracle; and the comparison of such rows.
+ROW_KEYS = ('E_raw', 'N_sv', 'T_sv', 'E_sv', 'flux_raw', 'N_leaving', 'res_energy', 'res_flux', 'N_emitted')
+
+
+def oracle_flux(sim):
+    """flux_raw of the engine: sum of v e over the particles of each subvolume, unnormalised (the expression of
+    test_gpu_spectral.oracle_bands with a single band)."""
+    P = sim.P
+    n = P.N
+    sv, mode, e = P.sv[:n].astype(int), P.mode[:n].astype(int), P.energy[:n]
+    v = sim.mat.group_vel_array.reshape(-1, 3)[mode]
+    F = np.zeros((sim.S, 3))
+    for d in range(3):
+        np.add.at(F[:, d], sv, v[:, d] * e)
+    return F
+
+
+def oracle_row(sim, flux_every=10):
+    """The step the oracle has just run, with the keys and shapes of one row of Engine.step: reservoir tallies of this step
+    only, flux_raw on heat-flux steps ((step + 1) % flux_every == 0) and NaN on the others, as the engine returns it."""
+    R, S = sim.R, sim.S
+    row = dict(E_raw=sim.E_raw.copy(), N_sv=sim.N_sv.astype(np.float64), T_sv=sim.T_sv.copy(), E_sv=sim.E_sv.copy(),
+               N_leaving=sim.N_leaving[:R].astype(np.float64), res_energy=sim.res_energy_step[:R].copy(),
+               res_flux=sim.res_flux_step[:R].copy(), N_emitted=float(sim.N_emitted))
+    row['flux_raw'] = oracle_flux(sim) if flux_every > 0 and sim.step % flux_every == 0 else np.full((S, 3), np.nan)
+    return row
+
+
+RUN_TOL = dict(tol_raw=TOL_RUN_ERAW, tol_flux=TOL_RUN_FLUX, tol_res=TOL_RUN_RES)
+
+
+def engine_row(t, s):
+    return {k: t[k][s] for k in ROW_KEYS}
+
+
+def assert_rows(t, s, row, tol_T=TOL_T, tol_E=TOL_E, tol_raw=TOL_ROW_ERAW, tol_flux=TOL_ROW_FLUX, tol_res=TOL_ROW_RES,
+                label=None):
+    """Row s of the engine's tallies `t` against `row` (oracle_row, or engine_row of another run): the counts exactly, the
+    reals to tolerance (recorded at the caller's line, one site per field).  E_raw, flux_raw and the reservoir tallies add
+    terms of either sign: relative to the row's largest |value|."""
+    where = 'step %d' % (s if label is None else label)
+    for k in ('N_sv', 'N_leaving', 'N_emitted'):
+        assert np.array_equal(t[k][s], row[k]), '%s differs at %s: %r against %r' % (k, where, t[k][s], row[k])
+    assert allclose(t['T_sv'][s], row['T_sv'], rtol=0, atol=tol_T, depth=2, tag='T_sv'), 'T_sv differs at ' + where
+    assert rel_err(t['E_sv'][s], row['E_sv'], depth=2, tag='E_sv', bound=tol_E) < tol_E, 'E_sv differs at ' + where
+    assert rel_row(t['E_raw'][s], row['E_raw'], depth=2, tag='E_raw', bound=tol_raw) <= tol_raw, 'E_raw differs at ' + where
+    f = t['flux_raw'][s]
+    assert np.array_equal(np.isnan(f), np.isnan(row['flux_raw'])), 'flux_raw on a different step at ' + where
+    if not np.isnan(f).all():
+        assert rel_row(f, row['flux_raw'], depth=2, tag='flux_raw', bound=tol_flux) <= tol_flux, 'flux_raw differs at ' + where
+    assert rel_row(t['res_energy'][s], row['res_energy'], depth=2, tag='res_energy', bound=tol_res) <= tol_res, \
+        'res_energy differs at ' + where
+    assert rel_row(t['res_flux'][s], row['res_flux'], depth=2, tag='res_flux', bound=tol_res) <= tol_res, \
+        'res_flux differs at ' + where
+
+
+def assert_runs_equal(t0, t1):
+    """Every row of two engine runs of the same steps (assert_rows; the second run against the first)."""
+    n = t0['N_sv'].shape[0]
+    assert t1['N_sv'].shape[0] == n
+    for s in range(n):
+        assert_rows(t1, s, engine_row(t0, s), **RUN_TOL)
 
 
 def sv_interp_of(ct, kind, interp):
