@@ -266,6 +266,52 @@ int nk_get_band_rows(nk_ctx *ctx, double *F, double *N, int64_t *steps, int32_t 
  * F [S*nbands*3], N [S*nbands], summed over the ranks with a communicator. */
 int nk_tally_bands_state(nk_ctx *ctx, double *F, double *N);
 
+/* Spatial field maps (the GPU-native counterpart of the reference's particle scatter plots, Population.plot_figures,
+ * Population.py:1841-1979, drawn at :123 and every 100 steps at :1735): particle count N, deviational energy E = sum e_i and
+ * heat flux F = sum v_i e_i on a uniform grid of n[0] x n[1] x n[2] cells of size h from corner lo, independent of the
+ * subvolumes.  Cell of a particle: floor((x - lo) * (1 / h)) per axis, an index outside [0, n) CLAMPED into the edge cell
+ * (and counted in `clamped`); cell index (ix * n[1] + iy) * n[2] + iz.  The sums are accumulated as 64-bit integers of terms
+ * scaled by 2^k_E / 2^k_F (nk_field_report): for given per-particle terms and scales the sums are the same bits whatever the
+ * order of the adds, the path (LDS / global) or the split of the particles over ranks, and every rank of a communicator holds
+ * the same field.  (Two RUNS of one ensemble on different rank counts still differ in the last bits of their subvolume
+ * temperatures, hence of the terms.) */
+typedef struct {
+    double lo[3], h[3];
+    int32_t n[3];            /* {0, 0, 0}: off (the default) -- nothing is launched or allocated */
+    int32_t every;           /* field steps: (step + 1) % every == 0; a positive multiple of nk_params.flux_every */
+    int32_t flags;           /* NK_FIELD_GLOBAL | NK_FIELD_TEST_SMALL_BOUND */
+    int64_t capacity;        /* 0: the scales follow the particle slots of the store(s); > 0: they allow for at least this many,
+                              * so that runs on stores of different sizes (other rank counts) derive the same k_E, k_F and
+                              * their integers can be compared or added */
+} nk_field;
+#define NK_FIELD_GLOBAL 1            /* never keep the bins in LDS (also: environment NK_FIELD_PATH=global); the result is the same bits */
+#define NK_FIELD_TEST_SMALL_BOUND 2  /* test hook: divide the bound B_E by 2^40, so that ordinary terms exceed it */
+/* NK_ERR_ARG: every <= 0 or not a multiple of flux_every, h <= 0, more than 2^24 cells, or before nk_set_material /
+ * nk_set_subvolumes / nk_set_params.  While a field is on, the resident kernel (NK_RESIDENT) is not used.  Step mode tallies
+ * right after the sweep of a field step with the tally's own e_i (so cells and the step's E_raw / flux_raw row sum the same
+ * terms); each field step's integer grid is summed over the ranks (ncclInt64) and added to a double accumulator. */
+int nk_set_field(nk_ctx *ctx, const nk_field *f);
+/* The sums over the field steps since the last reset: N [ncells], E [ncells], F [ncells*3] (any may be NULL), the number of
+ * field steps in them and the particles that were clamped; reset != 0 starts a new average.  A field step whose rough-wall
+ * migrants were not delivered is skipped and not counted in samples.  The same on every rank of a communicator. */
+int nk_get_field(nk_ctx *ctx, double *N, double *E, double *F, int64_t *samples, int64_t *clamped, int32_t reset);
+/* State mode: the particles where they stand, after the deferred relaxation, e_i against the occupation at each particle's
+ * interpolated temperature (or T_ref), as nk_tally_bands_state.  raw [ncells*8]: per cell the integers {N, E 2^k_E, Fx 2^k_F,
+ * Fy 2^k_F, Fz 2^k_F, 0, 0, 0} of this call alone (summed over the ranks of a communicator).  NK_ERR_CAPACITY, naming the
+ * sum, when a term exceeded its bound (never a silent wrap); nk_step reports the same for its field steps. */
+int nk_tally_field_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped);
+typedef struct {
+    int32_t n[3], every;
+    int64_t ncells;
+    int32_t k_E, k_F;        /* the integers hold e_i 2^k_E and v_i e_i 2^k_F, rounded to nearest */
+    double B_E, B_F;         /* bounds of |e_i| (eV) and |v_i e_i| the scales were derived from */
+    int64_t capacity;        /* particle slots of all ranks the scales allow for */
+    int64_t bytes;           /* device memory allocated for the field (0 when off) */
+    int32_t lds_path;        /* 1: bins in LDS with one flush per workgroup, 0: global integer adds directly */
+    int32_t on;
+} nk_field_report;
+int nk_field_info(nk_ctx *ctx, nk_field_report *out);
+
 /* device versions of the reference's primitives, for parity tests (tests/ -m gpu) */
 int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
                      double *xc, double *tc, int32_t *fc);                       /* Mesh.py:806-856 */

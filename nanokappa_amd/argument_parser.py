@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device` and `--spectral_bands`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands` and `--field_grid`."""
 import argparse
 import os
 import sys
@@ -52,6 +52,10 @@ def initialise_parser(debug_flag=False):
     a('--spectral_bands', default=['0', 'frequency'], type=str, nargs='*',
       help='N [frequency|branch] (or just: branch): tally the heat flux in N frequency bands, or one band per branch, on '
            'every heat-flux step and write the frequency-resolved conductivity to k_contribution.txt; 0 = off')
+    a('--field_grid', default=[], type=str, nargs='*',
+      help='nx ny nz [every]: sum particle count, energy and heat flux on a uniform grid of nx x ny x nz cells over the '
+           'bounding box every `every` steps (default 100, a multiple of 10) on the GPU, averaged over the convergence '
+           'window, and write field.vtk; the counterpart of the particle scatter of --fig_plot; off by default')
     return p
 
 

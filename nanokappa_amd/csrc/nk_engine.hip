@@ -19,6 +19,7 @@
 
 #include "../../include/nanokappa_hip.h"
 #include "nk_kernels.h"
+#include "nk_field.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -135,6 +136,9 @@ struct nk_ctx {
     size_t band_rows_n = 0;
     std::vector<double> band_rows;       // the rows of the last nk_step call: F [S][B][3], then N [S][B]
     std::vector<int64_t> band_steps;     //   and the absolute step of each
+    // spatial field maps (nk_set_field, k_field; nk_field.hip): off by default -- then nothing is launched or allocated
+    NkFieldHost field;
+    double res_T_max = 0.0;              // highest reservoir temperature (nk_set_reservoirs): bounds the field's terms
 };
 
 #define NK_HIP(call)                                                                                   \
@@ -444,6 +448,7 @@ void nk_destroy(nk_ctx *ctx) {
     if (ctx->band_map) hipFree(ctx->band_map);
     if (ctx->band_slabs) hipFree(ctx->band_slabs);
     if (ctx->band_rows_d) hipFree(ctx->band_rows_d);
+    nk_field_free(ctx->field);
     hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1015,6 +1020,7 @@ int nk_set_reservoirs(nk_ctx *ctx, const nk_reservoirs *r) {
     if (r->R > 0) {
         NK_UP(r->facet, (size_t)r->R, &d.res_facet);
         NK_UP(r->T, (size_t)r->R, &d.res_T);
+        ctx->res_T_max = *std::max_element(r->T, r->T + r->R);
         NK_UP(r->enter_prob, (size_t)r->R * d.M, &d.enter_prob);
         const double *c;
         NK_UP(r->counter, (size_t)r->R * d.M, &c);
@@ -1897,6 +1903,58 @@ static int nk_band_pass(nk_ctx *ctx, bool state, double *row_dev) {
     return NK_OK;
 }
 
+// ---- spatial field maps (k_field; nk_field.hip).  The bounds of the terms follow the temperatures the run can hold and the
+// scales the slots of the store (all ranks): both are looked at again at the start of every nk_step / nk_tally_field_state
+// call and after the store has grown -- places every rank of a communicator reaches together.
+static int nk_field_refresh(nk_ctx *ctx) {
+    NkFieldHost &F = ctx->field;
+    const NkDev &d = ctx->d;
+    const int fe = ctx->params.flux_every;
+    NK_ARG(fe > 0 && F.cfg.every % fe == 0, "field: every must be a positive multiple of flux_every");
+    // (host values only: nothing is copied or synchronised here; one rank pays two comparisons per nk_step call)
+    double T_hi = std::max(ctx->h_Tgrid.empty() ? 0.0 : ctx->h_Tgrid.back(), d.Tfill_hi);
+    if (!d.T_ref_local) T_hi = std::max(T_hi, d.T_ref);
+    if (d.R > 0) T_hi = std::max(T_hi, ctx->res_T_max);
+    if (T_hi != F.T_hi) {
+        F.T_hi = T_hi;
+        F.BE = d.kb * T_hi; F.BF = F.vmax * F.BE;
+        if (F.cfg.flags & NK_FIELD_TEST_SMALL_BOUND) F.BE = ldexp(F.BE, -40);
+        F.capacity = 0;
+    }
+    // One rank: the store's slots.  With a communicator the scales must be the same on every rank, so the slots are summed
+    // over the ranks -- a rank may have reserved on its own since the last call, which the others cannot know without asking:
+    // one small all-reduce per nk_step call, the price of integers that can be all-reduced.
+    double cap = (double)d.cap;
+    if (ctx->comm) { int rc = nk_comm_allreduce(ctx, &cap, 1); if (rc) return rc; }
+    const int64_t slots = std::max<int64_t>((int64_t)cap, F.cfg.capacity);      // (nk_field.capacity: a floor the caller chose)
+    if (slots != F.capacity) nk_field_scale(F, slots);
+    return NK_OK;
+}
+// One pass into the integer grid; summed over the ranks (integers: the result does not depend on who held which particle).
+static int nk_field_sample(nk_ctx *ctx, bool state) {
+    NkFieldHost &F = ctx->field;
+    NK_HIP(nk_field_pass(F, ctx->d, state, nk_lds(ctx, false), ctx->num_cu, ctx->stream));
+    if (ctx->comm) {
+        ncclResult_t nrc = ctx->rccl.AllReduce(F.grid, F.grid, ((size_t)F.ncells + 1) * 8, ncclInt64, ncclSum, ctx->comm, ctx->stream);
+        if (nrc != ncclSuccess) { ctx->err = "ncclAllReduce of the field grid failed"; return NK_ERR_COMM; }
+    }
+    return NK_OK;
+}
+// The status words {samples, clamped, overflow E, overflow F}; a term above its bound is an error that names the sum.
+static int nk_field_status(nk_ctx *ctx, long long st[4], const char *who) {
+    NkFieldHost &F = ctx->field;
+    NK_HIP(hipMemcpy(st, F.status, 4 * sizeof(long long), hipMemcpyDeviceToHost));
+    if (st[2] || st[3]) {
+        long long z[2] = {0, 0};
+        NK_HIP(hipMemcpy(F.status + 2, z, sizeof(z), hipMemcpyHostToDevice));
+        ctx->err = std::string(who) + ": field overflow: " + std::to_string(st[2]) + " term(s) of E above B_E = " + std::to_string(F.BE) +
+                   " eV, " + std::to_string(st[3]) + " term(s) of F above B_F = " + std::to_string(F.BF) +
+                   " (occupations outside the material's temperature range?); they were left out of the sums";
+        return NK_ERR_CAPACITY;
+    }
+    return NK_OK;
+}
+
 // Enqueue up to `nsteps` timesteps without host synchronisation, drain the stream, copy the history rows back.  A sweep that
 // sees a segment which COULD overflow at the following step raises the halt word; the remaining steps of the batch then do
 // nothing, *done < nsteps comes back, and nk_step grows the store (state intact, nothing dropped) and carries on.
@@ -2024,6 +2082,12 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
             int rcb_ = nk_band_pass(ctx, false, ctx->band_rows_d + band_s.size() * 4 * (size_t)S * ctx->band_B);
             if (rcb_) return rcb_;
             band_s.push_back(s);
+        }
+        // the field of the same particles on field steps (k_field; one launch per field step whatever the grid size)
+        if (ctx->field.on && do_flux && ((stepno + 1) % ctx->field.cfg.every) == 0) {
+            int rcf_ = nk_field_sample(ctx, false);
+            if (rcf_) return rcf_;
+            NK_HIP(nk_field_accumulate(ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
         }
         double *hrow = ctx->hist + (size_t)s * HROW;
         const bool ahead = tail_emit;                          // the next step's emission beside this step's tail (the last step's too: for the next call)
@@ -2212,6 +2276,7 @@ static inline bool nk_want_resident(const nk_ctx *ctx) {
     const NkDev &d = ctx->d;
     if (!getenv("NK_RESIDENT") || getenv("NK_NO_RESIDENT") || ctx->comm || d.nranks != 1 || d.Fr > 0 || d.mig_buf || d.qx || nk_geom_mode(ctx) != 1) return false;
     if (ctx->band_B > 0) return false;                 // the band-resolved flux pass runs between the launches of nk_step_batch
+    if (ctx->field.on) return false;                   // ... and so does the field pass
     if (d.res_gen == 2 || d.sv_interp == 3 || d.NB > 254 || d.S > 128 || d.nseg <= 0) return false;
     const int64_t lim = getenv("NK_RESIDENT_MAX") ? atoll(getenv("NK_RESIDENT_MAX")) : 1200000;
     return d.cap <= lim && nk_lds(ctx, true, 5) <= 160 * 1024;
@@ -2344,6 +2409,7 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
     double last_T[2] = {0, 0};
     ctx->band_rows.clear();
     ctx->band_steps.clear();
+    if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;
     while (s_out < nsteps) {
         int32_t nd = 0;
         if ((rc = nk_want_resident(ctx) ? nk_step_resident(ctx, nsteps - s_out, h, &nd) : nk_step_batch(ctx, nsteps - s_out, h, &nd))) return rc;
@@ -2409,6 +2475,7 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
                 if ((rc = nk_ensure_migration(ctx, want))) return rc;
             }
             if ((rc = nk_update_tau_window(ctx, false))) return rc;
+            if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;     // the store has grown: the field's scales follow
         }
     }
     ctx->timing.slots = d.cap;
@@ -2427,6 +2494,10 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
     }
     if (ctx->comm && !ctx->band_rows.empty()) {          // the band rows of the call: summed over the ranks in one all-reduce
         if ((rc = nk_comm_allreduce(ctx, ctx->band_rows.data(), (int64_t)ctx->band_rows.size()))) return rc;
+    }
+    if (ctx->field.on) {
+        long long st[4];
+        if ((rc = nk_field_status(ctx, st, "nk_step"))) return rc;
     }
     return NK_OK;
 }
@@ -2760,6 +2831,102 @@ int nk_tally_bands_state(nk_ctx *ctx, double *F, double *N) {
     if (ctx->comm && (rc = nk_comm_allreduce(ctx, h.data(), (int64_t)h.size()))) return rc;
     memcpy(F, h.data(), 3 * sb * sizeof(double));
     memcpy(N, h.data() + 3 * sb, sb * sizeof(double));
+    return NK_OK;
+}
+
+// ---- spatial field maps: Population.plot_figures (Population.py:1841-1979, drawn at :123 and every 100 steps at :1735) as sums
+// on a grid instead of a scatter of every particle
+int nk_set_field(nk_ctx *ctx, const nk_field *f) {
+    NK_ARG(ctx && f, "nk_set_field: bad arguments");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    nk_field_free(ctx->field);
+    if (f->n[0] == 0 && f->n[1] == 0 && f->n[2] == 0) return NK_OK;
+    NK_ARG(ctx->have_material && ctx->have_sv, "nk_set_field: set the material and the subvolumes first");
+    const NkDev &d = ctx->d;
+    std::vector<double> vg((size_t)d.M * 3);
+    NK_HIP(hipMemcpy(vg.data(), ctx->d_vg, vg.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double vmax = 0.0;
+    for (int m = 0; m < d.M; ++m) vmax = std::max(vmax, sqrt(vg[3 * m] * vg[3 * m] + vg[3 * m + 1] * vg[3 * m + 1] + vg[3 * m + 2] * vg[3 * m + 2]));
+    const double T_hi = std::max(ctx->h_Tgrid.empty() ? 0.0 : ctx->h_Tgrid.back(), d.Tfill_hi);
+    int rc = nk_field_configure(ctx->field, f, ctx->params.flux_every, d.kb, T_hi, vmax, ctx->err);
+    if (rc) return rc;
+    NK_ARG(f->capacity >= 0, "nk_set_field: capacity must not be negative");
+    nk_field_scale(ctx->field, std::max<int64_t>(std::max<int64_t>(d.cap, 1), f->capacity));   // (this rank's slots; nk_step looks again, over all ranks)
+    return NK_OK;
+}
+
+int nk_get_field(nk_ctx *ctx, double *N, double *E, double *F, int64_t *samples, int64_t *clamped, int32_t reset) {
+    NK_ARG(ctx, "nk_get_field: bad arguments");
+    NkFieldHost &fh = ctx->field;
+    NK_ARG(fh.on, "nk_get_field: no field was set (nk_set_field)");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t nc = (size_t)fh.ncells;
+    std::vector<double> a(nc * 5);
+    NK_HIP(hipMemcpy(a.data(), fh.acc, a.size() * sizeof(double), hipMemcpyDeviceToHost));
+    long long st[4];
+    int rc = nk_field_status(ctx, st, "nk_get_field");
+    if (rc) return rc;
+    for (size_t c = 0; c < nc; ++c) {
+        if (N) N[c] = a[5 * c];
+        if (E) E[c] = a[5 * c + 1];
+        if (F) { F[3 * c] = a[5 * c + 2]; F[3 * c + 1] = a[5 * c + 3]; F[3 * c + 2] = a[5 * c + 4]; }
+    }
+    if (samples) *samples = st[0];
+    if (clamped) *clamped = st[1];
+    if (reset) {
+        NK_HIP(hipMemset(fh.acc, 0, a.size() * sizeof(double)));
+        NK_HIP(hipMemset(fh.status, 0, 4 * sizeof(long long)));
+    }
+    return NK_OK;
+}
+
+int nk_tally_field_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped) {
+    NK_ARG(ctx && raw, "nk_tally_field_state: bad arguments");
+    NkFieldHost &fh = ctx->field;
+    NK_ARG(fh.on, "nk_tally_field_state: no field was set (nk_set_field)");
+    int rc = nk_check_ready(ctx);
+    if (rc) return rc;
+    NK_HIP(hipSetDevice(ctx->device));
+    NkDev &d = ctx->d;
+    if ((rc = nk_normalize(ctx))) return rc;
+    if (ctx->pending_relax) {                          // the state the caller means includes the deferred relaxation
+        k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 0);
+        ctx->pending_relax = false;
+    }
+    if ((rc = nk_field_refresh(ctx))) return rc;
+    if ((rc = nk_field_sample(ctx, true))) return rc;
+    const size_t nc = (size_t)fh.ncells;
+    std::vector<int64_t> h((nc + 1) * 8);
+    NK_HIP(hipMemcpyAsync(h.data(), fh.grid, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(nk_field_clear_grid(fh, ctx->stream));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    const int64_t *hdr = h.data() + nc * 8;
+    if (hdr[1] || hdr[2]) {
+        ctx->err = "nk_tally_field_state: field overflow: " + std::to_string((long long)hdr[1]) + " term(s) of E above B_E = " +
+                   std::to_string(fh.BE) + " eV, " + std::to_string((long long)hdr[2]) + " term(s) of F above B_F = " + std::to_string(fh.BF);
+        return NK_ERR_CAPACITY;
+    }
+    memcpy(raw, h.data(), nc * 8 * sizeof(int64_t));
+    if (clamped) *clamped = hdr[0];
+    return NK_OK;
+}
+
+int nk_field_info(nk_ctx *ctx, nk_field_report *out) {
+    NK_ARG(ctx && out, "nk_field_info: NULL argument");
+    memset(out, 0, sizeof(*out));
+    const NkFieldHost &fh = ctx->field;
+    if (!fh.on) return NK_OK;
+    for (int a = 0; a < 3; ++a) out->n[a] = fh.cfg.n[a];
+    out->every = fh.cfg.every;
+    out->ncells = fh.ncells;
+    out->k_E = fh.kE; out->k_F = fh.kF;
+    out->B_E = fh.BE; out->B_F = fh.BF;
+    out->capacity = fh.capacity;
+    out->bytes = fh.bytes;
+    out->lds_path = nk_field_lds_bins(fh, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_field_pass asks, too)
+    out->on = 1;
     return NK_OK;
 }
 

@@ -88,7 +88,21 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_specular_begin', 'nk_specular_pairs', 'nk_specular_end', 'nk_rough_begin', 'nk_rough_pairs', 'nk_rough_finish',
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
-           'nk_tally_bands_state']
+           'nk_tally_bands_state', 'nk_set_field', 'nk_get_field', 'nk_tally_field_state', 'nk_field_info']
+
+class nk_field(C.Structure):
+    _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
+                ('capacity', C.c_int64)]
+
+
+class nk_field_report(C.Structure):
+    _fields_ = [('n', C.c_int32 * 3), ('every', C.c_int32), ('ncells', C.c_int64), ('k_E', C.c_int32), ('k_F', C.c_int32),
+                ('B_E', C.c_double), ('B_F', C.c_double), ('capacity', C.c_int64), ('bytes', C.c_int64),
+                ('lds_path', C.c_int32), ('on', C.c_int32)]
+
+
+FIELD_GLOBAL = 1             # nk_set_field flags (include/nanokappa_hip.h)
+FIELD_TEST_SMALL_BOUND = 2
 
 _lib = None
 
@@ -148,6 +162,11 @@ def load_library():
     L.nk_set_bands.argtypes = [C.c_void_p, C.c_int32, c_ip]
     L.nk_get_band_rows.argtypes = [C.c_void_p, c_dp, c_dp, C.POINTER(C.c_int64), C.c_int32, c_ip]
     L.nk_tally_bands_state.argtypes = [C.c_void_p, c_dp, c_dp]
+    c_i64p = C.POINTER(C.c_int64)
+    L.nk_set_field.argtypes = [C.c_void_p, C.POINTER(nk_field)]
+    L.nk_get_field.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
+    L.nk_tally_field_state.argtypes = [C.c_void_p, c_i64p, c_i64p]
+    L.nk_field_info.argtypes = [C.c_void_p, C.POINTER(nk_field_report)]
     _lib = L
     return L
 
@@ -423,6 +442,62 @@ class Engine(object):
         F, N = np.zeros((S, B, 3)), np.zeros((S, B))
         self._ck(self.L.nk_tally_bands_state(self.h, _p(F), _p(N)), 'nk_tally_bands_state')
         return F, N
+
+    # ------------------------------------------------------- spatial field maps
+    def set_field(self, lo, h, n, every, flags=0, capacity=0):
+        """Sum particle count, deviational energy and heat flux on a uniform grid of n = (nx, ny, nz) cells of size h from
+        corner lo, on every step with (step + 1) % every == 0 (a multiple of flux_every) (nk_set_field; k_field).  n = (0, 0, 0)
+        turns it off.  flags: FIELD_GLOBAL forces the global-memory path (same bits as the LDS path).  capacity > 0: derive the
+        integer scales for at least this many particle slots (the same k_E, k_F on stores of different sizes)."""
+        f = nk_field()
+        n = [int(v) for v in np.ravel(n)]
+        if len(n) != 3:
+            raise NkError('set_field: n must have three entries')
+        if any(n):
+            lo, h = _d(lo).ravel(), _d(h).ravel()
+            if lo.shape[0] != 3 or h.shape[0] != 3:
+                raise NkError('set_field: lo and h must have three entries')
+            for a in range(3):
+                f.lo[a], f.h[a] = lo[a], h[a]
+        for a in range(3):
+            f.n[a] = n[a]
+        f.every, f.flags, f.capacity = int(every), int(flags), int(capacity)
+        self._field_n = None
+        self._ck(self.L.nk_set_field(self.h, C.byref(f)), 'nk_set_field')
+        self._field_n = tuple(n) if any(n) else None
+
+    def field_info(self):
+        """nk_field_info: cells, scales (the integers hold e 2^k_E and v e 2^k_F), bounds, bytes allocated, path in use."""
+        r = nk_field_report()
+        self._ck(self.L.nk_field_info(self.h, C.byref(r)), 'nk_field_info')
+        return dict(n=tuple(r.n), every=int(r.every), ncells=int(r.ncells), k_E=int(r.k_E), k_F=int(r.k_F), B_E=r.B_E, B_F=r.B_F,
+                    capacity=int(r.capacity), bytes=int(r.bytes), lds_path=int(r.lds_path), on=int(r.on))
+
+    def field(self, reset=False):
+        """The sums over the field steps since the last reset (all ranks): dict N, E (nx, ny, nz), F (nx, ny, nz, 3), samples
+        (field steps in the sums) and clamped (particles outside the grid, counted in its edge cells)."""
+        if getattr(self, '_field_n', None) is None:
+            raise NkError('field: no field was set (set_field)')
+        n = self._field_n
+        N, E, F = np.zeros(n), np.zeros(n), np.zeros(n + (3,))
+        sm, cl = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.nk_get_field(self.h, _p(N), _p(E), _p(F), C.byref(sm), C.byref(cl), 1 if reset else 0), 'nk_get_field')
+        return dict(N=N, E=E, F=F, samples=int(sm.value), clamped=int(cl.value))
+
+    def tally_field_state(self):
+        """State mode (nk_tally_field_state): the raw integers of the particles where they stand, after the relaxation, e
+        against each particle's interpolated temperature.  dict raw (nx, ny, nz, 8) int64 = {N, E 2^k_E, F 2^k_F (3), 0, 0, 0},
+        k_E, k_F, clamped, and the reals N, E, F they stand for."""
+        if getattr(self, '_field_n', None) is None:
+            raise NkError('tally_field_state: no field was set (set_field)')
+        n = self._field_n
+        raw = np.zeros(n + (8,), dtype=np.int64)
+        cl = C.c_int64(0)
+        self._ck(self.L.nk_tally_field_state(self.h, raw.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cl)), 'nk_tally_field_state')
+        info = self.field_info()
+        kE, kF = info['k_E'], info['k_F']
+        return dict(raw=raw, k_E=kE, k_F=kF, clamped=int(cl.value), N=raw[..., 0].astype(np.float64),
+                    E=np.ldexp(raw[..., 1].astype(np.float64), -kE), F=np.ldexp(raw[..., 2:5].astype(np.float64), -kF))
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

@@ -48,6 +48,8 @@ def main(argv=None):
     pop.view.postprocess()
     if pop.n_bands > 0 and pop.rank == 0:
         pop.write_k_contribution()
+    if pop.field_n is not None and pop.rank == 0:
+        pop.write_field()
     total = datetime.now() - start
     print('Total time: %s' % total)
     if out is not None:

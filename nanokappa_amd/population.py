@@ -21,6 +21,7 @@ import numpy as np
 from .constants import Constants
 from . import setup_tables as ST
 from . import spectral as SP
+from . import field as FD
 from .engine import Engine
 from .sharding import shard_range
 
@@ -188,6 +189,13 @@ class Population(Constants):
         nb, kind = spectral_bands_option(getattr(args, 'spectral_bands', None))
         if nb > 0:
             self.set_bands(kind, nb, phonon)
+        # spatial field maps (--field_grid nx ny nz [every]; off by default): the GPU-native counterpart of --fig_plot's scatter
+        self.field_n = None
+        fn, fev = FD.field_grid_option(getattr(args, 'field_grid', None))
+        if fn is not None:
+            self.set_field(fn, fev, geometry)
+        elif getattr(args, 'fig_plot', None) and self.rank == 0:
+            print('--fig_plot is not drawn by this build; --field_grid nx ny nz [every] writes the same quantities on a grid (field.vtk)')
         if comm is not None:               # nk_comm_init decides what one rank needs (rank / nranks; NK_FORCE_COMM)
             self.engine.comm_init(comm[0], self.rank, self.nranks)
         J = phonon.number_of_branches
@@ -268,6 +276,68 @@ class Population(Constants):
             return None
         return SP.write_k_contribution(SP.k_contribution_path(self.results_folder_name), self.band_edges, self.band_kind,
                                        self._geo.subvol_connections, v.mean_band_k, v.std_band_k, self.current_timestep)
+
+    # ----------------------------------------------------------------------- spatial field maps
+    def set_field(self, n, every=FD.FIELD_EVERY_DEFAULT, geometry=None):
+        """Sum N, E, F on a uniform grid of n = (nx, ny, nz) cells over geometry.bounds on every `every`-th step (a multiple of
+        n_dt_to_conv) from here on (Engine.set_field); n = None: off."""
+        geometry = geometry if geometry is not None else self._geo
+        self._field_last = None
+        if n is None:
+            self.engine.set_field((0, 0, 0), (1, 1, 1), (0, 0, 0), 1)
+            self.field_n = None
+            return
+        if every % self.n_dt_to_conv:
+            raise ValueError('--field_grid: every (%d) must be a multiple of %d, the heat-flux cadence' % (every, self.n_dt_to_conv))
+        self.field_lo, self.field_h, self.field_n = FD.grid_from_bounds(geometry.bounds, n)
+        self.field_every = int(every)
+        self.engine.set_field(self.field_lo, self.field_h, self.field_n, self.field_every)
+        # The averaging window, in steps on the engine's absolute clock: the field steps of n_mean convergence rows (the window
+        # of _Stats), a whole number of them and at least one.  A window ends -- the accumulator is read and restarted --
+        # whenever current_timestep is a multiple of it; run() cuts its library calls there, so what a window holds does not
+        # depend on how the run is cut into calls.
+        self.field_window = max(1, (max(self.n_mean, 1) * self.n_dt_to_conv) // self.field_every) * self.field_every
+        self._field_last = None                                 # the latest complete window (Engine.field dict)
+
+    def _field_window_end(self):
+        """current_timestep is a multiple of field_window: keep the window that ends here and start the next."""
+        last = self.engine.field(reset=True)
+        if last['samples'] > 0:
+            self._field_last = last
+
+    def field(self):
+        """The field, normalised the reference's way per cell (field.normalise): dict N (mean particles per cell and field
+        step), energy (eV/angstrom^3), T (K), heat_flux (W/m^2) shaped (nx, ny, nz[, 3]), samples, clamped, lo, h, n.  It is the
+        mean over the latest COMPLETE window -- field_window steps, the field steps of n_mean convergence rows, always the
+        same number of samples (field_window / every, less the field steps the engine had to skip) -- and, until the first window is complete, over the field steps so far.
+        Cells without particles are NaN."""
+        if self.field_n is None:
+            raise RuntimeError('field: no grid (--field_grid or Population.set_field)')
+        raw = self._field_last if self._field_last is not None else self.engine.field()
+        geo, ph = self._geo, self._ph
+        S = self.n_of_subvols
+        cen = FD.cell_centres(self.field_lo, self.field_h, self.field_n).reshape(-1, 3)
+        sv = geo.subvol_classifier.predict(cen) if S > 1 else np.zeros(cen.shape[0], dtype=int)
+        if self.T_reference == 'local':                         # Population.py:706-708: the subvolume's own reference
+            ref = np.asarray(ph.crystal_energy_function(self._window_T()))[sv]
+        else:
+            ref = np.full(cen.shape[0], float(self.ref_en_density))
+        out = FD.normalise(raw['N'], raw['E'], raw['F'], raw['samples'], ph.number_of_active_modes,
+                           ph.number_of_qpoints * ph.volume_unitcell, self.eVpsa2_in_Wm2, norm=self.norm,
+                           particle_density=self.particle_density, cell_volume=float(np.prod(self.field_h)),
+                           ref_energy=ref.reshape(self.field_n), temperature_function=ph.temperature_function)
+        out.update(samples=raw['samples'], clamped=raw['clamped'], lo=self.field_lo, h=self.field_h, n=self.field_n)
+        return out
+
+    def write_field(self):
+        if self.field_n is None or not self.results_folder_name:
+            return None
+        f = self.field()
+        if f['samples'] == 0:
+            return None
+        return FD.write_vtk(FD.field_path(self.results_folder_name), f['lo'], f['h'], f['n'], f['N'], f['T'], f['energy'],
+                            f['heat_flux'], title='nanokappa field: mean over %d field steps up to timestep %d'
+                            % (f['samples'], self.current_timestep))
 
     # ----------------------------------------------------------------------------------- setup
     def _shard(self, n):
@@ -703,6 +773,8 @@ class Population(Constants):
             self.current_timestep = es
             self.t = es * self.dt
             self.restart_reservoir_balance()
+            if getattr(self, 'field_n', None) is not None:      # the field's window in progress no longer lines up: start again
+                self.engine.field(reset=True)
 
     # ------------------------------------------------------------------------------- time loop
     def run_timestep(self, geometry, phonon):
@@ -723,6 +795,9 @@ class Population(Constants):
             if (self.current_timestep % 100) == 0:
                 self._every_hundred(geometry)
             chunk = min(nsteps - done, 100 - (self.current_timestep % 100))
+            field_on = getattr(self, 'field_n', None) is not None
+            if field_on:                                        # ... and at the ends of the field's averaging windows
+                chunk = min(chunk, self.field_window - (self.current_timestep % self.field_window))
             # the reference grows its arrays as the ensemble grows; here the particle store is re-laid out with head room
             # before it can fill up (this rank's share of N_p against the engine's slots)
             # (the engine's slot count only changes when the store grows: asked for again after every 100 steps and after a reserve)
@@ -763,6 +838,8 @@ class Population(Constants):
                     self.restart_reservoir_balance()
                 s0 = s1
             done += chunk
+            if field_on and (self.current_timestep % self.field_window) == 0:
+                self._field_window_end()
 
     def _every_hundred(self, geometry):
         if self.results_folder_name and getattr(self.args, 'checkpoint', True):     # every rank: its shard of the particles
@@ -770,6 +847,8 @@ class Population(Constants):
         self.view.postprocess(verbose=False)
         if self.n_bands > 0 and self.rank == 0:
             self.write_k_contribution()
+        if getattr(self, 'field_n', None) is not None and self.rank == 0:     # (the accumulator is the same on every rank)
+            self.write_field()
         self.update_residue(geometry)
         info = 'Timestep {:>5d} - max residue: {:>9.3e} ({:<9s}) ['.format(int(self.current_timestep), self.max_residue, self.max_residue_qt)
         for sv in range(self.n_of_subvols):

@@ -1,0 +1,179 @@
+"""Host side of the spatial field maps (nanokappa_amd/field.py; no GPU): the float64 sums against an independent histogram of
+the reference's own frozen-step particles, slice-aligned grids against the golden subvolume sums, the quantised sums, the
+normalisations against the golden subvolume energies and temperatures, VTK round trip and the --field_grid option."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from util import golden, sub, golden_phonon, TOL_E, TOL_T
+
+from nanokappa_amd import field as FD
+
+
+def frozen(variant='lin'):
+    """Particles of the frozen step (tests/golden/step.npz) where calculate_energy saw them: positions, e_i, v_i."""
+    gs = sub(golden('step'), variant)
+    gm = sub(golden('mesh'), 'box200ttp')
+    ph = golden_phonon()
+    m = gs['mid_modes']
+    v = ph.group_vel[m[:, 0], m[:, 1]]
+    return gs, gm, ph, gs['mid_positions'], gs['energies'], v
+
+
+def slice_grid(gm, per_slice=1, ny=1, nz=1):
+    S, a = int(gm['n_of_subvols']), int(gm['slice_axis'])
+    n = [ny, nz, nz]
+    n[a] = per_slice * S
+    return FD.grid_from_bounds(gm['bounds'], n), S, a
+
+
+def per_slice(a, axis, S):
+    a = np.moveaxis(np.asarray(a), axis, 0)
+    return a.reshape((S, a.shape[0] // S) + a.shape[1:]).sum(axis=(1, 2, 3))
+
+
+def test_grid_from_bounds():
+    lo, h, n = FD.grid_from_bounds([[0, -10, 5], [200, 10, 25]], (20, 4, 5))
+    assert np.array_equal(lo, [0, -10, 5]) and np.array_equal(h, [10, 5, 4]) and n == (20, 4, 5)
+    with pytest.raises(ValueError):
+        FD.grid_from_bounds([[0, 0, 0], [1, 1, 1]], (4, 0, 4))
+    with pytest.raises(ValueError):
+        FD.grid_from_bounds([[0, 0, 0], [1, 0, 1]], (4, 4, 4))
+    c = FD.cell_centres(lo, h, n)
+    assert c.shape == (20, 4, 5, 3) and np.array_equal(c[0, 0, 0], [5, -7.5, 7]) and np.array_equal(c[-1, -1, -1], [195, 7.5, 23])
+
+
+@pytest.mark.parametrize('variant', ['lin', 'near', 'fixed', 'tref'])
+def test_sums_against_histogramdd(variant):
+    gs, gm, ph, x, e, v = frozen(variant)
+    assert e.shape[0] == x.shape[0] <= 20020
+    (lo, h, n), S, a = slice_grid(gm, 2, 4, 4)
+    f = FD.field_from_particles(x, e, v, lo, h, n)
+    # independent: np.histogramdd on explicit edges, the outermost ones opened so that particles outside land in the edge cells
+    edges = [lo[k] + h[k] * np.arange(n[k] + 1) for k in range(3)]
+    for ed in edges:
+        ed[0], ed[-1] = -np.inf, np.inf
+    N0 = np.histogramdd(x, bins=edges)[0]
+    E0 = np.histogramdd(x, bins=edges, weights=e)[0]
+    assert np.array_equal(f['N'], N0)
+    assert f['N'].sum() == x.shape[0]
+    assert np.max(np.abs(f['E'] - E0)) <= 1e-12 * np.max(np.abs(E0))
+    for k in range(3):
+        F0 = np.histogramdd(x, bins=edges, weights=v[:, k] * e)[0]
+        assert np.max(np.abs(f['F'][..., k] - F0)) <= 1e-12 * np.max(np.abs(f['F']))
+
+
+@pytest.mark.parametrize('variant', ['lin', 'near', 'fixed', 'tref'])
+def test_slice_aligned_grid_gives_the_subvolume_sums(variant):
+    gs, gm, ph, x, e, v = frozen(variant)
+    for shape in ((1, 1, 1), (2, 4, 4), (3, 2, 5)):
+        (lo, h, n), S, a = slice_grid(gm, *shape)
+        f = FD.field_from_particles(x, e, v, lo, h, n)
+        assert np.array_equal(per_slice(f['N'], a, S), gs['post_subvol_N_p'])
+        # every particle's slice is the reference's subvol_id, the clamped ones included
+        c, out = FD.cell_index(x, lo, h, n)
+        assert np.array_equal(c[:, a] // shape[0], gs['post_subvol_id'])
+        assert f['clamped'] == int(out.sum())
+        # the reference's un-normalised sums per subvolume (Population.py:712-716, :734-736)
+        sv = gs['post_subvol_id']
+        E0 = np.array([e[sv == s].sum() for s in range(S)])
+        F0 = np.array([(v[sv == s] * e[sv == s, None]).sum(axis=0) for s in range(S)])
+        assert np.max(np.abs(per_slice(f['E'], a, S) - E0)) <= 1e-12 * np.max(np.abs(E0))
+        assert np.max(np.abs(per_slice(f['F'], a, S) - F0)) <= 1e-12 * np.max(np.abs(F0))
+
+
+def test_quantised_within_the_rounding_bound_and_clamping():
+    gs, gm, ph, x, e, v = frozen('lin')
+    (lo, h, n), S, a = slice_grid(gm, 2, 4, 4)
+    f = FD.field_from_particles(x, e, v, lo, h, n)
+    for kE, kF in ((50, 40), (30, 25), (12, 10)):
+        q = FD.quantised(x, e, v, lo, h, n, kE, kF)
+        assert q['raw'].dtype == np.int64 and np.array_equal(q['N'], f['N']) and q['clamped'] == f['clamped']
+        assert not q['raw'][..., 5:].any()
+        slack = 1e-15 * np.max(np.abs(f['E']))                                      # (the float sums' own rounding)
+        assert np.all(np.abs(q['E'] - f['E']) <= f['N'] * np.ldexp(1.0, -(kE + 1)) + slack)
+        slack = 1e-15 * np.max(np.abs(f['F']))
+        assert np.all(np.abs(q['F'] - f['F']) <= f['N'][..., None] * np.ldexp(1.0, -(kF + 1)) + slack)
+    # integer sums do not depend on the order of the particles
+    p = np.random.default_rng(1).permutation(x.shape[0])
+    assert np.array_equal(FD.quantised(x[p], e[p], v[p], lo, h, n, 50, 40)['raw'], FD.quantised(x, e, v, lo, h, n, 50, 40)['raw'])
+    # on the upper faces and outside: edge cells, counted in clamped; on the lower faces: first cell, not clamped
+    lo, h, n = FD.grid_from_bounds([[0, 0, 0], [4, 4, 4]], (4, 4, 4))
+    pts = np.array([[4.0, 1.5, 1.5], [5.0, 1.5, 1.5], [-0.25, 1.5, 1.5], [0.0, 0.0, 0.0], [3.999, 4.0, -1.0], [1.0, 2.0, 3.0]])
+    c, out = FD.cell_index(pts, lo, h, n)
+    assert np.array_equal(c, [[3, 1, 1], [3, 1, 1], [0, 1, 1], [0, 0, 0], [3, 3, 0], [1, 2, 3]])
+    assert np.array_equal(out, [True, True, True, False, True, False])
+    f = FD.field_from_particles(pts, np.ones(6), np.tile([1.0, 2.0, 3.0], (6, 1)), lo, h, n)
+    assert f['clamped'] == 4 and f['N'][3, 1, 1] == 2 and f['N'].sum() == 6 and np.array_equal(f['F'][3, 1, 1], [2, 4, 6])
+
+
+@pytest.mark.parametrize('variant', ['lin', 'near', 'fixed', 'tref'])
+def test_normalise_gives_the_golden_subvolume_energy_and_temperature(variant):
+    """One cell per subvolume: field.normalise is calculate_energy + refresh_temperatures (Population.py:704-728, :692) and
+    calculate_heat_flux (:730-747).  The reference term of 'local' is evaluated at the temperatures before the refresh."""
+    from nanokappa_amd.constants import Constants
+    gs, gm, ph, x, e, v = frozen(variant)
+    (lo, h, n), S, a = slice_grid(gm)
+    f = FD.field_from_particles(x, e, v, lo, h, n)
+    if variant == 'tref':
+        ref = np.full(S, float(ph.crystal_energy_function(300.0)))
+    else:
+        ref = np.asarray(ph.crystal_energy_function(gs['mid_subvol_temperature']))
+    out = FD.normalise(f['N'], f['E'], f['F'], 1, ph.number_of_active_modes, ph.number_of_qpoints * ph.volume_unitcell,
+                       Constants().eVpsa2_in_Wm2, norm=('fixed' if variant == 'fixed' else 'mean'),
+                       particle_density=float(gs['particle_density']), cell_volume=float(np.prod(h)),
+                       ref_energy=ref.reshape(n), temperature_function=ph.temperature_function)
+    E, T = out['energy'].reshape(S), out['T'].reshape(S)
+    assert np.max(np.abs(E - gs['post_subvol_energy']) / np.abs(gs['post_subvol_energy'])) <= TOL_E
+    assert np.max(np.abs(T - gs['post_subvol_temperature'])) <= TOL_T
+    phi = out['heat_flux'].reshape(S, 3)
+    assert np.max(np.abs(phi - gs['heat_flux'])) <= 1e-12 * np.max(np.abs(gs['heat_flux']))
+    # empty cells are NaN; several samples: 'mean' is the ratio of the sums, 'fixed' divides by the samples
+    N2, E2, F2 = np.zeros((2, 1, 1)), np.zeros((2, 1, 1)), np.zeros((2, 1, 1, 3))
+    N2[0], E2[0], F2[0] = 30.0, 3.0, [3.0, 0.0, -3.0]
+    for norm, want in (('mean', 3.0 * 7 / 30.0 / 2.0), ('fixed', 3.0 / 3 * 7 / (0.5 * 8.0) / 2.0)):
+        o = FD.normalise(N2, E2, F2, 3, 7, 2.0, 10.0, norm=norm, particle_density=0.5, cell_volume=8.0)
+        assert np.isnan(o['energy'][1, 0, 0]) and np.all(np.isnan(o['heat_flux'][1])) and o['T'] is None
+        assert o['energy'][0, 0, 0] == pytest.approx(want, rel=1e-15) and o['N'][0, 0, 0] == 10.0
+        assert o['heat_flux'][0, 0, 0] == pytest.approx([want * 10, 0.0, -want * 10], rel=1e-15)
+
+
+def test_vtk_round_trip(tmp_path):
+    rng = np.random.default_rng(4)
+    n = (5, 3, 4)
+    lo, h = np.array([0.5, -2.0, 1e-3]), np.array([10.0, 0.1, 1.0 / 3.0])
+    N, T, E, F = rng.integers(0, 9, n).astype(float), 300 + rng.random(n), rng.random(n), rng.standard_normal(n + (3,))
+    T[1, 2, 3] = E[1, 2, 3] = np.nan
+    F[1, 2, 3] = np.nan
+    path = FD.write_vtk(str(tmp_path / 'field.vtk'), lo, h, n, N, T, E, F, title='a title')
+    txt = open(path).read().split('\n')
+    assert txt[0].startswith('# vtk DataFile') and txt[1] == 'a title' and txt[2] == 'ASCII' and txt[3] == 'DATASET STRUCTURED_POINTS'
+    assert 'DIMENSIONS 6 4 5' in txt and 'CELL_DATA 60' in txt and 'VECTORS heat_flux double' in txt
+    # VTK's order: x runs fastest
+    i = txt.index('SCALARS N double 1')
+    assert [float(t) for t in txt[i + 2:i + 2 + 6]] == [N[0, 0, 0], N[1, 0, 0], N[2, 0, 0], N[3, 0, 0], N[4, 0, 0], N[0, 1, 0]]
+    r = FD.read_vtk(path)
+    assert r['n'] == n and np.array_equal(r['lo'], lo) and np.array_equal(r['h'], h)
+    for k, a in (('N', N), ('T', T), ('energy', E), ('heat_flux', F)):
+        assert np.array_equal(r[k], a, equal_nan=True), k
+
+
+def test_field_grid_option_and_parser(capsys):
+    from nanokappa_amd.argument_parser import initialise_parser
+    assert FD.field_grid_option(None) == (None, 100) and FD.field_grid_option([]) == (None, 100)
+    assert FD.field_grid_option(['8', '4', '4']) == ((8, 4, 4), 100)
+    assert FD.field_grid_option(['8', '4', '4', '10']) == ((8, 4, 4), 10)
+    assert FD.field_grid_option(['0', '0', '0'])[0] is None
+    for bad in (['8'], ['8', '4'], ['8', '4', '4', '10', '1'], ['8', 'x', '4'], ['8', '0', '4'], ['8', '4', '-4'], ['8', '4', '4', '0'],
+                ['4096', '4096', '2']):
+        with pytest.raises(ValueError, match='--field_grid'):
+            FD.field_grid_option(bad)
+    p = initialise_parser()
+    req = ['--poscar_file', 'POSCAR', '--hdf_file', 'synthetic']
+    assert p.parse_args(req).field_grid == []
+    assert FD.field_grid_option(p.parse_args(req + ['--field_grid', '16', '16', '32', '50']).field_grid) == ((16, 16, 32), 50)
+    a = p.parse_args(req + ['--fig_plot', 'T', 'e'])               # still accepted
+    assert a.fig_plot == ['T', 'e'] and a.field_grid == []
