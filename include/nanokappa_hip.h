@@ -312,6 +312,46 @@ typedef struct {
 } nk_field_report;
 int nk_field_info(nk_ctx *ctx, nk_field_report *out);
 
+/* Mode-resolved tally: the distribution itself, E[s][m] = sum e_i and N[s][m] over the particles of subvolume s in mode
+ * m = q*J + j, at full resolution (S x M bins).  The group velocity is a property of the mode, so the heat flux of a mode is
+ * v_m E[s][m] exactly, and any band sum of nk_set_bands is a sum of entries of this table.  One pass over the store per mode
+ * step, one wave per segment: the modes are partitioned over the segments, so a wave keeps the bins of its segment's modes
+ * in LDS and writes its rows of the table with plain stores (owner path); without the partition, or when the bins do not fit,
+ * the adds go to the table in global memory (global path).  The sums are 64-bit integers of terms scaled by 2^k_E
+ * (nk_modes_report; the field's bound and scale rule): the same bits on either path, from run to run and for any split of the
+ * particles over ranks. */
+typedef struct {
+    int32_t every;           /* 0: off (the default) -- nothing is launched or allocated; else mode steps are the steps with
+                              * (step + 1) % every == 0, a positive multiple of nk_params.flux_every */
+    int32_t flags;           /* NK_MODES_GLOBAL | NK_MODES_TEST_SMALL_BOUND */
+    int64_t capacity;        /* as nk_field.capacity: a floor under the particle slots the scale allows for */
+} nk_modes;
+#define NK_MODES_GLOBAL 1            /* never keep the bins in LDS (also: environment NK_MODES_PATH=global); the result is the same bits */
+#define NK_MODES_TEST_SMALL_BOUND 2  /* test hook: divide the bound B_E by 2^40, so that ordinary terms exceed it */
+/* NK_ERR_ARG: every < 0 or not a multiple of flux_every, or before nk_set_material / nk_set_subvolumes / nk_set_params;
+ * NK_ERR_HIP (with the size) when the tables cannot be allocated.  While the tally is on, the resident kernel (NK_RESIDENT)
+ * is not used.  Step mode tallies right after the sweep of a mode step with the tally's own e_i (so the table and the step's
+ * E_raw / N_sv / flux_raw row sum the same terms). */
+int nk_set_modes(nk_ctx *ctx, const nk_modes *m);
+/* The sums over the mode steps since the last reset: N [S*M], E [S*M] (index s*M + m, m = q*J + j; either may be NULL), the
+ * number of mode steps in them and of mode steps that were skipped (rough-wall migrants not delivered on some rank); all
+ * ranks together (every rank takes or drops the same samples); reset != 0 starts a new average.  NK_ERR_CAPACITY, naming
+ * the sum, when a term exceeded its bound (never a silent wrap); nk_step reports the same for its mode steps. */
+int nk_get_modes(nk_ctx *ctx, double *N, double *E, int64_t *samples, int64_t *skipped, int32_t reset);
+/* State mode: the particles where they stand, after the deferred relaxation, e_i against the occupation at each particle's
+ * interpolated temperature (or T_ref), as nk_tally_field_state.  The raw integers N [S*M], E 2^k_E [S*M] of this call alone,
+ * summed over the ranks of a communicator. */
+int nk_tally_modes_state(nk_ctx *ctx, int64_t *N, int64_t *E);
+typedef struct {
+    int32_t every, k_E;      /* the integers hold e_i 2^k_E */
+    double B_E;              /* bound of |e_i| (eV) the scale was derived from */
+    int64_t capacity;        /* particle slots of all ranks the scale allows for */
+    int64_t bytes;           /* device memory allocated for the tally (0 when off) */
+    int32_t owner_path;      /* 1: wave-private bins in LDS and plain stores, 0: global integer adds */
+    int32_t on;
+} nk_modes_report;
+int nk_modes_info(nk_ctx *ctx, nk_modes_report *out);
+
 /* device versions of the reference's primitives, for parity tests (tests/ -m gpu) */
 int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
                      double *xc, double *tc, int32_t *fc);                       /* Mesh.py:806-856 */

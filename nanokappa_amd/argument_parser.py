@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands` and `--field_grid`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid` and `--mode_tally`."""
 import argparse
 import os
 import sys
@@ -56,6 +56,10 @@ def initialise_parser(debug_flag=False):
       help='nx ny nz [every]: sum particle count, energy and heat flux on a uniform grid of nx x ny x nz cells over the '
            'bounding box every `every` steps (default 100, a multiple of 10) on the GPU, averaged over the convergence '
            'window, and write field.vtk; the counterpart of the particle scatter of --fig_plot; off by default')
+    a('--mode_tally', default=['0'], type=str, nargs='*',
+      help='[every]: tally energy and particle count per (subvolume, mode) every `every` steps (default 100, a multiple of '
+           'n_dt_to_conv = 10) on the GPU over the convergence window, and write mode_tally.npz and the conductivity '
+           'accumulated over the mean free path, k_accumulation.txt; 0 = off (the default)')
     return p
 
 

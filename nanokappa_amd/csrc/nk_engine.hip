@@ -20,6 +20,7 @@
 #include "../../include/nanokappa_hip.h"
 #include "nk_kernels.h"
 #include "nk_field.h"
+#include "nk_modes.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -138,6 +139,8 @@ struct nk_ctx {
     std::vector<int64_t> band_steps;     //   and the absolute step of each
     // spatial field maps (nk_set_field, k_field; nk_field.hip): off by default -- then nothing is launched or allocated
     NkFieldHost field;
+    // mode-resolved tally (nk_set_modes, k_modes; nk_modes.hip): off by default -- then nothing is launched or allocated
+    NkModesHost modes;
     double res_T_max = 0.0;              // highest reservoir temperature (nk_set_reservoirs): bounds the field's terms
 };
 
@@ -449,6 +452,7 @@ void nk_destroy(nk_ctx *ctx) {
     if (ctx->band_slabs) hipFree(ctx->band_slabs);
     if (ctx->band_rows_d) hipFree(ctx->band_rows_d);
     nk_field_free(ctx->field);
+    nk_modes_free(ctx->modes);
     hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1955,6 +1959,62 @@ static int nk_field_status(nk_ctx *ctx, long long st[4], const char *who) {
     return NK_OK;
 }
 
+// ---- mode-resolved tally (k_modes; nk_modes.hip).  Bound and scale as the field's, looked at again at the same places.
+static double nk_modes_T_hi(const nk_ctx *ctx) {
+    const NkDev &d = ctx->d;
+    double T_hi = std::max(ctx->h_Tgrid.empty() ? 0.0 : ctx->h_Tgrid.back(), d.Tfill_hi);
+    if (!d.T_ref_local) T_hi = std::max(T_hi, d.T_ref);
+    if (d.R > 0) T_hi = std::max(T_hi, ctx->res_T_max);
+    return T_hi;
+}
+static int nk_modes_refresh(nk_ctx *ctx) {
+    NkModesHost &Mo = ctx->modes;
+    const NkDev &d = ctx->d;
+    const int fe = ctx->params.flux_every;
+    NK_ARG(fe > 0 && Mo.cfg.every % fe == 0, "modes: every must be a positive multiple of flux_every");
+    const double T_hi = nk_modes_T_hi(ctx);
+    if (T_hi != Mo.T_hi) nk_modes_bound(Mo, d.kb, T_hi);
+    // (with a communicator the scale must be the same on every rank: the slots are summed over the ranks, as for the field)
+    double cap = (double)d.cap;
+    if (ctx->comm) { int rc = nk_comm_allreduce(ctx, &cap, 1); if (rc) return rc; }
+    const int64_t slots = std::max<int64_t>((int64_t)cap, Mo.cfg.capacity);
+    if (slots != Mo.capacity) nk_modes_scale(Mo, slots);
+    return NK_OK;
+}
+// One pass into the sample table.  With a communicator only the header (overflow E, ran, skip) is summed over the ranks, so that
+// every rank takes or drops the same samples; the table stays this rank's own (it is tens of megabytes).
+static int nk_modes_sample(nk_ctx *ctx, bool state) {
+    NkModesHost &Mo = ctx->modes;
+    NK_HIP(nk_modes_pass(Mo, ctx->d, state, nk_lds(ctx, false), ctx->num_cu, ctx->stream));
+    if (ctx->comm) {
+        ncclResult_t nrc = ctx->rccl.AllReduce(Mo.hdr, Mo.hdr, 8, ncclInt64, ncclSum, ctx->comm, ctx->stream);
+        if (nrc != ncclSuccess) { ctx->err = "ncclAllReduce of the mode tally's header failed"; return NK_ERR_COMM; }
+    }
+    return NK_OK;
+}
+// The status words {samples, skipped, overflow E, -}; a term above its bound is an error that names the sum.
+static int nk_modes_status(nk_ctx *ctx, long long st[4], const char *who) {
+    NkModesHost &Mo = ctx->modes;
+    NK_HIP(hipMemcpy(st, Mo.status, 4 * sizeof(long long), hipMemcpyDeviceToHost));
+    if (st[2]) {
+        long long z = 0;
+        NK_HIP(hipMemcpy(Mo.status + 2, &z, sizeof(z), hipMemcpyHostToDevice));
+        ctx->err = std::string(who) + ": mode tally overflow: " + std::to_string(st[2]) + " term(s) of E above B_E = " + std::to_string(Mo.BE) +
+                   " eV (occupations outside the material's temperature range?); they were left out of the sums";
+        return NK_ERR_CAPACITY;
+    }
+    return NK_OK;
+}
+
+// [M][S] (the device's order: a segment's wave writes whole rows) -> [S][M] (the interface's)
+extern "C++" {
+template <typename TI, typename TO>
+static void nk_modes_transpose(const TI *in, TO *out, int M, int S) {
+    for (int m = 0; m < M; ++m)
+        for (int s = 0; s < S; ++s) out[(size_t)s * M + m] = (TO)in[(size_t)m * S + s];
+}
+}
+
 // Enqueue up to `nsteps` timesteps without host synchronisation, drain the stream, copy the history rows back.  A sweep that
 // sees a segment which COULD overflow at the following step raises the halt word; the remaining steps of the batch then do
 // nothing, *done < nsteps comes back, and nk_step grows the store (state intact, nothing dropped) and carries on.
@@ -2088,6 +2148,12 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
             int rcf_ = nk_field_sample(ctx, false);
             if (rcf_) return rcf_;
             NK_HIP(nk_field_accumulate(ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
+        }
+        // the mode-resolved tally of the same particles on mode steps (k_modes: one wave per segment)
+        if (ctx->modes.on && do_flux && ((stepno + 1) % ctx->modes.cfg.every) == 0) {
+            int rcm_ = nk_modes_sample(ctx, false);
+            if (rcm_) return rcm_;
+            NK_HIP(nk_modes_accumulate(ctx->modes, ctx->comm ? ctx->comm_nranks : 1, ctx->num_cu, ctx->stream));
         }
         double *hrow = ctx->hist + (size_t)s * HROW;
         const bool ahead = tail_emit;                          // the next step's emission beside this step's tail (the last step's too: for the next call)
@@ -2277,6 +2343,7 @@ static inline bool nk_want_resident(const nk_ctx *ctx) {
     if (!getenv("NK_RESIDENT") || getenv("NK_NO_RESIDENT") || ctx->comm || d.nranks != 1 || d.Fr > 0 || d.mig_buf || d.qx || nk_geom_mode(ctx) != 1) return false;
     if (ctx->band_B > 0) return false;                 // the band-resolved flux pass runs between the launches of nk_step_batch
     if (ctx->field.on) return false;                   // ... and so does the field pass
+    if (ctx->modes.on) return false;                   // ... and the mode tally's
     if (d.res_gen == 2 || d.sv_interp == 3 || d.NB > 254 || d.S > 128 || d.nseg <= 0) return false;
     const int64_t lim = getenv("NK_RESIDENT_MAX") ? atoll(getenv("NK_RESIDENT_MAX")) : 1200000;
     return d.cap <= lim && nk_lds(ctx, true, 5) <= 160 * 1024;
@@ -2410,6 +2477,7 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
     ctx->band_rows.clear();
     ctx->band_steps.clear();
     if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;
+    if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;
     while (s_out < nsteps) {
         int32_t nd = 0;
         if ((rc = nk_want_resident(ctx) ? nk_step_resident(ctx, nsteps - s_out, h, &nd) : nk_step_batch(ctx, nsteps - s_out, h, &nd))) return rc;
@@ -2476,6 +2544,7 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
             }
             if ((rc = nk_update_tau_window(ctx, false))) return rc;
             if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;     // the store has grown: the field's scales follow
+            if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;     // ... and the mode tally's
         }
     }
     ctx->timing.slots = d.cap;
@@ -2498,6 +2567,10 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
     if (ctx->field.on) {
         long long st[4];
         if ((rc = nk_field_status(ctx, st, "nk_step"))) return rc;
+    }
+    if (ctx->modes.on) {
+        long long st[4];
+        if ((rc = nk_modes_status(ctx, st, "nk_step"))) return rc;
     }
     return NK_OK;
 }
@@ -2926,6 +2999,119 @@ int nk_field_info(nk_ctx *ctx, nk_field_report *out) {
     out->capacity = fh.capacity;
     out->bytes = fh.bytes;
     out->lds_path = nk_field_lds_bins(fh, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_field_pass asks, too)
+    out->on = 1;
+    return NK_OK;
+}
+
+// ---- mode-resolved tally: E and N per (subvolume, mode)
+int nk_set_modes(nk_ctx *ctx, const nk_modes *m) {
+    NK_ARG(ctx && m, "nk_set_modes: bad arguments");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    nk_modes_free(ctx->modes);
+    if (m->every == 0) return NK_OK;
+    NK_ARG(ctx->have_material && ctx->have_sv, "nk_set_modes: set the material and the subvolumes first");
+    const NkDev &d = ctx->d;
+    const double T_hi = std::max(ctx->h_Tgrid.empty() ? 0.0 : ctx->h_Tgrid.back(), d.Tfill_hi);
+    int rc = nk_modes_configure(ctx->modes, m, ctx->params.flux_every, (int64_t)d.M * d.S, d.kb, T_hi, ctx->err);
+    if (rc) return rc;
+    nk_modes_scale(ctx->modes, std::max<int64_t>(std::max<int64_t>(d.cap, 1), m->capacity));   // (this rank's slots; nk_step looks again, over all ranks)
+    return NK_OK;
+}
+
+int nk_get_modes(nk_ctx *ctx, double *N, double *E, int64_t *samples, int64_t *skipped, int32_t reset) {
+    NK_ARG(ctx, "nk_get_modes: bad arguments");
+    NkModesHost &Mo = ctx->modes;
+    NK_ARG(Mo.on, "nk_get_modes: the mode tally is off (nk_set_modes)");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    const NkDev &d = ctx->d;
+    const size_t nb = (size_t)Mo.nbins;
+    long long st[4];
+    int rc = nk_modes_status(ctx, st, "nk_get_modes");
+    if (rc) return rc;
+    if (N || E) {
+        std::vector<double> a(nb);
+        // the accumulators are per rank: summed over the ranks here, once, on a copy (ncclDouble)
+        double *tmp = nullptr;
+        if (ctx->comm) NK_HIP(hipMalloc((void **)&tmp, nb * 8));
+        for (int w = 0; w < 2; ++w) {
+            double *out = w ? E : N;
+            if (!out) continue;
+            const double *src = w ? Mo.accE : Mo.accN;
+            if (ctx->comm) {
+                hipError_t he = hipMemcpyAsync(tmp, src, nb * 8, hipMemcpyDeviceToDevice, ctx->stream);
+                ncclResult_t nrc = he == hipSuccess ? ctx->rccl.AllReduce(tmp, tmp, nb, ncclDouble, ncclSum, ctx->comm, ctx->stream) : ncclSystemError;
+                if (he == hipSuccess && nrc == ncclSuccess) he = hipStreamSynchronize(ctx->stream);
+                if (he != hipSuccess || nrc != ncclSuccess) { hipFree(tmp); ctx->err = "nk_get_modes: the all-reduce of the accumulators failed"; return NK_ERR_COMM; }
+                src = tmp;
+            }
+            hipError_t he = hipMemcpy(a.data(), src, nb * 8, hipMemcpyDeviceToHost);
+            if (he != hipSuccess) { if (tmp) hipFree(tmp); NK_HIP(he); }
+            nk_modes_transpose(a.data(), out, d.M, d.S);
+        }
+        if (tmp) hipFree(tmp);
+    }
+    if (samples) *samples = st[0];
+    if (skipped) *skipped = st[1];
+    if (reset) {
+        NK_HIP(hipMemset(Mo.accE, 0, nb * 8));
+        NK_HIP(hipMemset(Mo.accN, 0, nb * 8));
+        NK_HIP(hipMemset(Mo.status, 0, 4 * sizeof(long long)));
+    }
+    return NK_OK;
+}
+
+int nk_tally_modes_state(nk_ctx *ctx, int64_t *N, int64_t *E) {
+    NK_ARG(ctx && N && E, "nk_tally_modes_state: bad arguments");
+    NkModesHost &Mo = ctx->modes;
+    NK_ARG(Mo.on, "nk_tally_modes_state: the mode tally is off (nk_set_modes)");
+    int rc = nk_check_ready(ctx);
+    if (rc) return rc;
+    NK_HIP(hipSetDevice(ctx->device));
+    NkDev &d = ctx->d;
+    if ((rc = nk_normalize(ctx))) return rc;
+    if (ctx->pending_relax) {                          // the state the caller means includes the deferred relaxation
+        k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 0);
+        ctx->pending_relax = false;
+    }
+    if ((rc = nk_modes_refresh(ctx))) return rc;
+    if ((rc = nk_modes_sample(ctx, true))) return rc;
+    const size_t nb = (size_t)Mo.nbins;
+    if (ctx->comm) {                                   // integers: the sum does not depend on who held which particle
+        ncclResult_t nrc = ctx->rccl.AllReduce(Mo.tE, Mo.tE, nb, ncclInt64, ncclSum, ctx->comm, ctx->stream);
+        if (nrc == ncclSuccess) nrc = ctx->rccl.AllReduce(Mo.tN, Mo.tN, nb, ncclInt32, ncclSum, ctx->comm, ctx->stream);
+        if (nrc != ncclSuccess) { ctx->err = "ncclAllReduce of the mode table failed"; return NK_ERR_COMM; }
+    }
+    std::vector<int64_t> hE(nb);
+    std::vector<int32_t> hN(nb);
+    long long hdr[8];
+    NK_HIP(hipMemcpyAsync(hE.data(), Mo.tE, nb * 8, hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemcpyAsync(hN.data(), Mo.tN, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemcpyAsync(hdr, Mo.hdr, sizeof(hdr), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemsetAsync(Mo.hdr, 0, sizeof(hdr), ctx->stream));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    nk_modes_transpose(hE.data(), E, d.M, d.S);
+    nk_modes_transpose(hN.data(), N, d.M, d.S);
+    if (hdr[0]) {
+        ctx->err = "nk_tally_modes_state: mode tally overflow: " + std::to_string(hdr[0]) + " term(s) of E above B_E = " +
+                   std::to_string(Mo.BE) + " eV; they were left out of the sums";
+        return NK_ERR_CAPACITY;
+    }
+    return NK_OK;
+}
+
+int nk_modes_info(nk_ctx *ctx, nk_modes_report *out) {
+    NK_ARG(ctx && out, "nk_modes_info: NULL argument");
+    memset(out, 0, sizeof(*out));
+    const NkModesHost &Mo = ctx->modes;
+    if (!Mo.on) return NK_OK;
+    out->every = Mo.cfg.every;
+    out->k_E = Mo.kE;
+    out->B_E = Mo.BE;
+    out->capacity = Mo.capacity;
+    out->bytes = Mo.bytes;
+    out->owner_path = nk_modes_owner(Mo, ctx->d, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_modes_pass asks, too)
     out->on = 1;
     return NK_OK;
 }

@@ -29,6 +29,8 @@ void nk_field_free(NkFieldHost &F);
 // validate f against the engine's state and allocate; kb in eV/K, T_hi the highest temperature an occupation can stand for,
 // vmax the largest group speed; NK_ERR_* with `err` set
 int nk_field_configure(NkFieldHost &F, const nk_field *f, int flux_every, double kb, double T_hi, double vmax, std::string &err);
+// the largest k with capacity B 2^k <= 2^62 (shared with the mode tally, nk_modes.hip)
+int nk_field_k(double B, int64_t capacity);
 // k_E, k_F for `capacity` particle slots
 void nk_field_scale(NkFieldHost &F, int64_t capacity);
 // one pass over the store into F.grid; lds0: bytes of LDS the subvolume tables take (nk_lds(ctx, false))

@@ -35,7 +35,7 @@ void nk_field_free(NkFieldHost &F) {
 // with the largest k for which capacity B 2^k <= 2^62 the int64 sum stays below 2^62 + capacity / 2 < 2^63: it cannot wrap.
 // The kernel checks every term against B and reports a larger one (occupations uploaded from outside that range) instead of
 // adding it.  Re-derived when the store grows (nk_step).
-static int nk_field_k(double B, int64_t capacity) {
+int nk_field_k(double B, int64_t capacity) {
     const double m = B * (double)std::max<int64_t>(capacity, 1);
     int ex = 0;
     (void)frexp(m, &ex);                        // m = f 2^ex, 0.5 <= f < 1: m 2^k <= 2^62 for k = 62 - ex

@@ -2328,6 +2328,138 @@ __global__ void k_field_finish(NkFieldDev f, long long *status, int nranks) {
     for (int k = 0; k < 8; ++k) hdr[k] = 0ull;
 }
 
+// =================================================================================== mode-resolved tally
+// The solution itself: E[m][s] = sum e_i and N[m][s] over the particles of subvolume s in mode m = q * J + j, at full
+// resolution (M x S bins: 3.6 million at BASELINE config 2).  A pass of its own over the store, which it only reads, with the
+// two modes of k_spectral / k_field (STATE = false: the sweep's own terms, nk_tally_e; STATE = true: a snapshot after the
+// relaxation, e against the occupation at the particle's interpolated temperature or T_ref).
+// The modes are partitioned over the segments (nk_device.h), so whoever walks one segment needs nl x S bins and no others, and
+// on this rank is the only writer of those rows of the table.  A workgroup of 16 waves walks `nteam` segments at a time, one
+// TEAM of 16 / nteam waves per segment (nteam = 16: one wave per segment; the host takes the largest nteam whose bins leave room
+// for two workgroups per CU -- 4 at config 2, where a segment's bins are 14 KB):
+//   owner = 1: a team's bins live in its own slice of LDS (behind the subvolume tables, at byte offset lds0 + team * slice:
+//     nlmax * S u64 of E, then nlmax * S u32 of N), integer LDS adds, and at the end of the segment the team writes all its
+//     nl x S bins -- zeros included -- with plain stores to the rows of the GLOBAL mode index (sm.mode(l): the segmentation
+//     changes when the store is regrown, the table does not).  No global atomics, no clearing between samples.
+//   owner = 0 (no partition: a stored index is the mode itself; or bins that do not fit): the host clears the table and
+//     every add is a 64-bit / 32-bit integer add to it (global_atomic_add_x2, global_atomic_add).
+// Integers as in k_field: rint(e 2^k_E) added as int64 in two's complement, a term above B_E is not added but counted in the
+// header.  Same integers on either path, for any launch shape and any split of the particles over ranks.
+// Table: tE [M * S] (u64, bin m * S + s), tN [M * S] (u32); header hdr[8] = {overflow E, ran, skip, -, ...}.
+struct NkModesDev {
+    double sE, BE;                    // 2^k_E, bound of |e|
+    unsigned long long *tE;           // [M * S]
+    unsigned int *tN;                 // [M * S]
+    unsigned long long *hdr;          // [8]
+    int32_t owner, lds0, slice;       // slice: bytes of one team's bins (a multiple of 16)
+    int32_t nteam;                    // segments a workgroup walks at a time: 1, 2, 4, 8 or 16
+};
+#define NK_MODES_WG 1024
+template <bool STATE>
+__global__ __launch_bounds__(NK_MODES_WG) void k_modes(NkDev d, NkModesDev m) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (!STATE && d.halt[0]) return;                 // a halted batch: the sweep did nothing at this step
+    NkLds L;
+    nk_lds_setup<0, 0>(d, smem, L);
+    const int S = d.S, nteam = m.nteam, tsize = NK_MODES_WG / nteam;          // threads of a team (whole waves)
+    const int team = threadIdx.x / tsize, tl = threadIdx.x - team * tsize;
+    unsigned long long *bE = (unsigned long long *)(smem + m.lds0 + (size_t)team * m.slice);      // [nlmax * S]
+    unsigned int *bN = (unsigned int *)(bE + (size_t)d.nlmax * S);                                  // [nlmax * S]
+    if (m.owner) {
+        for (int b = tl; b < d.nlmax * S; b += tsize) { bE[b] = 0ull; bN[b] = 0u; }
+        __syncthreads();
+    }
+    unsigned int n_ovE = 0, stuck = 0;
+    const uint32_t lbmask = (1u << d.lb) - 1u;
+    const int ngroups = (d.nseg + nteam - 1) / nteam;
+    // (every thread of the workgroup takes the same trips through this loop: the barriers are met by all)
+    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+        const int seg = grp * nteam + team;
+        const bool live = seg < d.nseg;
+        const int64_t base = live ? (int64_t)seg * d.segcap + (d.seg_lo ? d.seg_lo[seg] : 0) : 0;
+        const int count = live ? d.seg_count[seg] : 0;
+        // step mode: migrants that k_deliver could not place wait in the inbox -- the sweep tallied particles this pass
+        // cannot see, so the sample is dropped (header `skip`)
+        if (!STATE && live && d.mig_buf && tl == 0 && d.mig_n[seg] > 0) stuck = 1;
+        const NkSegModes sm = nk_seg_modes(d, live ? seg : 0);
+        const int nb = (m.owner && live) ? sm.nl * S : 0;
+        for (int k = tl; k < count; k += tsize) {
+            const int64_t i = base + k;
+            const int idx = (int)(d.w0[i] & lbmask);
+            const NkMode *rec = sm.rec + idx;
+            const double x = d.x[i], y = d.y[i], z = d.z[i];
+            const int s = nk_classify(d, L.tb, x, y, z);
+            double e;
+            if (STATE) {
+                double invT;
+                const double T = nk_interp_T(d, L.tb, x, y, z, invT);
+                const double n0 = !d.T_ref_local ? nk_occupation(d, d.T_ref, rec->omega, rec->E0)
+                                                 : (T > 0.0 ? nk_be(rec->omega * d.c_hk, rec->E0, invT, d.invT0) : 0.0);
+                e = d.hbar * rec->omega * (d.occ[i] - n0);
+            } else {
+                e = nk_tally_e(d, L.tb, s, d.occ[i], rec->omega, rec->E0);
+            }
+            const bool okE = fabs(e) <= m.BE;                                     // (false for a NaN as well)
+            n_ovE += okE ? 0u : 1u;
+            const unsigned long long qE = okE ? (unsigned long long)(long long)rint(e * m.sE) : 0ull;
+            if (m.owner) {
+                // (a stored index beyond the segment's own modes cannot occur with the partition; it must not leave the slice)
+                const int b = (idx < sm.nl ? idx : 0) * S + s;
+                atomicAdd(bN + b, 1u);
+                atomicAdd(bE + b, qE);
+            } else {
+                const int gmode = sm.mode(idx);
+                if ((unsigned)gmode >= (unsigned)d.M) continue;                    // (no such mode: cannot occur; never outside the table)
+                const int64_t b = (int64_t)gmode * S + s;
+                atomicAdd(m.tN + b, 1u);
+                atomicAdd(m.tE + b, qE);
+            }
+        }
+        if (m.owner) {
+            __syncthreads();
+            // the team's rows to the table; every bin goes back to zero in the hands of the thread that read it
+            for (int b = tl; b < nb; b += tsize) {
+                const int l = b / S, gmode = sm.mode(l);
+                const unsigned long long vE = bE[b];
+                const unsigned int vN = bN[b];
+                bE[b] = 0ull; bN[b] = 0u;
+                if ((unsigned)gmode >= (unsigned)d.M) continue;
+                const int64_t o = (int64_t)gmode * S + (b - l * S);
+                m.tE[o] = vE;
+                m.tN[o] = vN;
+            }
+            __syncthreads();
+        }
+    }
+    if (n_ovE) atomicAdd(m.hdr + 0, (unsigned long long)n_ovE);
+    if (stuck) atomicAdd(m.hdr + 2, 1ull);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(m.hdr + 1, 1ull);         // this rank's pass ran
+}
+// One sample's integers into the window's sums, in element order: accE[b] += tE[b] / 2^k_E, accN[b] += tN[b] (doubles; the
+// headroom of the integers is spent per sample, not per window).  The accumulators are this rank's own: with a communicator
+// only the header has been summed over the ranks, so that every rank takes or drops the same samples -- a sample counts only
+// if the pass ran on every rank (`ran` = nranks: not in a halted batch) and no rank saw undelivered migrants (`skip` = 0).
+template <int NK_TU = 0>
+__global__ __launch_bounds__(256) void k_modes_accum(NkModesDev m, double *accE, double *accN, int64_t n, int nranks) {
+    const bool take = m.hdr[1] == (unsigned long long)nranks && m.hdr[2] == 0ull;
+    if (!take) return;
+    const double iE = 1.0 / m.sE;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < n; b += stride) {
+        accE[b] += (double)(long long)m.tE[b] * iE;
+        accN[b] += (double)m.tN[b];
+    }
+}
+// ... and the header into the running status {samples, skipped, overflow E, -}; the header is cleared.
+template <int NK_TU = 0>
+__global__ void k_modes_finish(NkModesDev m, long long *status, int nranks) {
+    const bool take = m.hdr[1] == (unsigned long long)nranks && m.hdr[2] == 0ull;
+    if (take) status[0] += 1;
+    else if (m.hdr[1] == (unsigned long long)nranks) status[1] += 1;      // (a halted batch's steps are walked again: not skipped)
+    status[2] += (long long)m.hdr[0];
+    for (int k = 0; k < 8; ++k) m.hdr[k] = 0ull;
+}
+
 // contains_check (Population.py:1712-1722) + Mesh.sample_volume (Mesh.py:890-904)
 template <int GEOM>
 __global__ __launch_bounds__(NK_WG) void k_contains(NkDev d, uint32_t step) {

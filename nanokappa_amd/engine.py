@@ -88,7 +88,8 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_specular_begin', 'nk_specular_pairs', 'nk_specular_end', 'nk_rough_begin', 'nk_rough_pairs', 'nk_rough_finish',
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
-           'nk_tally_bands_state', 'nk_set_field', 'nk_get_field', 'nk_tally_field_state', 'nk_field_info']
+           'nk_tally_bands_state', 'nk_set_field', 'nk_get_field', 'nk_tally_field_state', 'nk_field_info',
+           'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -101,6 +102,17 @@ class nk_field_report(C.Structure):
                 ('lds_path', C.c_int32), ('on', C.c_int32)]
 
 
+class nk_modes(C.Structure):
+    _fields_ = [('every', C.c_int32), ('flags', C.c_int32), ('capacity', C.c_int64)]
+
+
+class nk_modes_report(C.Structure):
+    _fields_ = [('every', C.c_int32), ('k_E', C.c_int32), ('B_E', C.c_double), ('capacity', C.c_int64), ('bytes', C.c_int64),
+                ('owner_path', C.c_int32), ('on', C.c_int32)]
+
+
+MODES_GLOBAL = 1             # nk_set_modes flags (include/nanokappa_hip.h)
+MODES_TEST_SMALL_BOUND = 2
 FIELD_GLOBAL = 1             # nk_set_field flags (include/nanokappa_hip.h)
 FIELD_TEST_SMALL_BOUND = 2
 
@@ -167,6 +179,10 @@ def load_library():
     L.nk_get_field.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
     L.nk_tally_field_state.argtypes = [C.c_void_p, c_i64p, c_i64p]
     L.nk_field_info.argtypes = [C.c_void_p, C.POINTER(nk_field_report)]
+    L.nk_set_modes.argtypes = [C.c_void_p, C.POINTER(nk_modes)]
+    L.nk_get_modes.argtypes = [C.c_void_p, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
+    L.nk_tally_modes_state.argtypes = [C.c_void_p, c_i64p, c_i64p]
+    L.nk_modes_info.argtypes = [C.c_void_p, C.POINTER(nk_modes_report)]
     _lib = L
     return L
 
@@ -498,6 +514,48 @@ class Engine(object):
         kE, kF = info['k_E'], info['k_F']
         return dict(raw=raw, k_E=kE, k_F=kF, clamped=int(cl.value), N=raw[..., 0].astype(np.float64),
                     E=np.ldexp(raw[..., 1].astype(np.float64), -kE), F=np.ldexp(raw[..., 2:5].astype(np.float64), -kF))
+
+    # ------------------------------------------------------- mode-resolved tally
+    def set_modes(self, every, flags=0, capacity=0):
+        """Tally energy and particle count per (subvolume, mode) on every step with (step + 1) % every == 0 (a multiple of
+        flux_every) (nk_set_modes; k_modes).  every = 0 turns it off and frees its tables.  flags: MODES_GLOBAL forces the
+        global-memory path (same bits as the owner path).  capacity > 0: derive the integer scale for at least this many
+        particle slots (the same k_E on stores of different sizes)."""
+        m = nk_modes()
+        m.every, m.flags, m.capacity = int(every), int(flags), int(capacity)
+        self._modes_on = False
+        self._ck(self.L.nk_set_modes(self.h, C.byref(m)), 'nk_set_modes')
+        self._modes_on = int(every) != 0
+
+    def modes_info(self):
+        """nk_modes_info: cadence, scale (the integers hold e 2^k_E), bound, bytes allocated, path in use."""
+        r = nk_modes_report()
+        self._ck(self.L.nk_modes_info(self.h, C.byref(r)), 'nk_modes_info')
+        return dict(every=int(r.every), k_E=int(r.k_E), B_E=r.B_E, capacity=int(r.capacity), bytes=int(r.bytes),
+                    owner_path=int(r.owner_path), on=int(r.on))
+
+    def modes(self, reset=False):
+        """The sums over the mode steps since the last reset (all ranks): dict N, E [S, Q, J], samples (mode steps in the
+        sums) and skipped (mode steps dropped because rough-wall migrants were waiting undelivered)."""
+        if not getattr(self, '_modes_on', False):
+            raise NkError('modes: the mode tally is off (set_modes)')
+        shape = (self.S, self.M // self.J, self.J)
+        N, E = np.zeros(shape), np.zeros(shape)
+        sm, sk = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.nk_get_modes(self.h, _p(N), _p(E), C.byref(sm), C.byref(sk), 1 if reset else 0), 'nk_get_modes')
+        return dict(N=N, E=E, samples=int(sm.value), skipped=int(sk.value))
+
+    def tally_modes_state(self):
+        """State mode (nk_tally_modes_state): the raw integers of the particles where they stand, after the relaxation, e
+        against each particle's interpolated temperature (or T_ref).  dict N_raw, E_raw [S, Q, J] int64 (E 2^k_E), k_E, and
+        the reals N, E they stand for."""
+        if not getattr(self, '_modes_on', False):
+            raise NkError('tally_modes_state: the mode tally is off (set_modes)')
+        shape = (self.S, self.M // self.J, self.J)
+        N, E = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        self._ck(self.L.nk_tally_modes_state(self.h, N.ctypes.data_as(C.POINTER(C.c_int64)), E.ctypes.data_as(C.POINTER(C.c_int64))), 'nk_tally_modes_state')
+        kE = self.modes_info()['k_E']
+        return dict(N_raw=N, E_raw=E, k_E=kE, N=N.astype(np.float64), E=np.ldexp(E.astype(np.float64), -kE))
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

@@ -50,6 +50,8 @@ def main(argv=None):
         pop.write_k_contribution()
     if pop.field_n is not None and pop.rank == 0:
         pop.write_field()
+    if pop.modes_every > 0:
+        pop.write_modes()                    # (every rank: the read-out sums over the ranks; rank 0 writes)
     total = datetime.now() - start
     print('Total time: %s' % total)
     if out is not None:

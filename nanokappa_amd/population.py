@@ -22,6 +22,7 @@ from .constants import Constants
 from . import setup_tables as ST
 from . import spectral as SP
 from . import field as FD
+from . import modes as MD
 from .engine import Engine
 from .sharding import shard_range
 
@@ -196,6 +197,11 @@ class Population(Constants):
             self.set_field(fn, fev, geometry)
         elif getattr(args, 'fig_plot', None) and self.rank == 0:
             print('--fig_plot is not drawn by this build; --field_grid nx ny nz [every] writes the same quantities on a grid (field.vtk)')
+        # mode-resolved tally (--mode_tally [every]; off by default): E and N per (subvolume, mode) on the device
+        self.modes_every = 0
+        mev = MD.mode_tally_option(getattr(args, 'mode_tally', None), self.n_dt_to_conv)
+        if mev > 0:
+            self.set_modes(mev)
         if comm is not None:               # nk_comm_init decides what one rank needs (rank / nranks; NK_FORCE_COMM)
             self.engine.comm_init(comm[0], self.rank, self.nranks)
         J = phonon.number_of_branches
@@ -338,6 +344,79 @@ class Population(Constants):
         return FD.write_vtk(FD.field_path(self.results_folder_name), f['lo'], f['h'], f['n'], f['N'], f['T'], f['energy'],
                             f['heat_flux'], title='nanokappa field: mean over %d field steps up to timestep %d'
                             % (f['samples'], self.current_timestep))
+
+    # ----------------------------------------------------------------------- mode-resolved tally
+    def set_modes(self, every=FD.FIELD_EVERY_DEFAULT):
+        """Tally energy and particle count per (subvolume, mode) on every `every`-th step (a multiple of n_dt_to_conv) from
+        here on (Engine.set_modes); every = 0 or None: off."""
+        self._modes_last = None
+        every = int(every or 0)
+        if every == 0:
+            self.engine.set_modes(0)
+            self.modes_every = 0
+            return
+        if every < 0 or every % self.n_dt_to_conv:
+            raise ValueError('--mode_tally: every (%d) must be a positive multiple of %d, the heat-flux cadence' % (every, self.n_dt_to_conv))
+        self.engine.set_modes(every)
+        self.modes_every = every
+        # the averaging window: the mode steps of n_mean convergence rows, as the field's (set_field)
+        self.modes_window = max(1, (max(self.n_mean, 1) * self.n_dt_to_conv) // every) * every
+
+    def _modes_window_end(self):
+        """current_timestep is a multiple of modes_window: keep the window that ends here and start the next."""
+        last = self.engine.modes(reset=True)
+        if last['samples'] > 0:
+            last.update(step=int(self.current_timestep), T=self._window_T())
+            self._modes_last = last
+
+    def mode_distribution(self):
+        """The table: dict N, E [S, Q, J] (sums over `samples` mode steps), samples, skipped, step, T [S] (the window-mean
+        subvolume temperatures).  The latest COMPLETE window -- modes_window steps, the mode steps of n_mean convergence rows --
+        and, until the first window is complete, the mode steps so far.  (With several ranks every rank must call this.)"""
+        if self.modes_every <= 0:
+            raise RuntimeError('mode_distribution: the tally is off (--mode_tally or Population.set_modes)')
+        if self._modes_last is not None:
+            return self._modes_last
+        d = self.engine.modes()
+        d.update(step=int(self.current_timestep), T=self._window_T())
+        return d
+
+    def mode_k(self, dist=None):
+        """Conductivity contribution of every mode to every subvolume connection [C, M] (modes.mode_k): dT from the
+        window-mean temperatures, normalised by all particles of the connection's two subvolumes, as band_k."""
+        d = dist if dist is not None else self.mode_distribution()
+        ph, geo = self._ph, self._geo
+        return MD.mode_k(d['E'], d['N'], ph.group_vel, geo.subvol_connections, geo.subvol_con_vectors, d['T'],
+                         ph.number_of_active_modes, ph.number_of_qpoints * ph.volume_unitcell, self.eVpsa2_in_Wm2, self.a_in_m)
+
+    def kappa_accumulation(self, by='mfp', points=200, dist=None):
+        """Conductivity accumulated over the mean free path (by='mfp': |v| tau at the mean of the window's temperatures) or the
+        frequency (by='frequency') of the modes: dict x [M], grid [G], k [C, G] (cumulative, the last point = the total), k_mode."""
+        if by not in ('mfp', 'frequency'):
+            raise ValueError("kappa_accumulation: by must be 'mfp' or 'frequency'")
+        d = dist if dist is not None else self.mode_distribution()
+        ph = self._ph
+        if by == 'mfp':
+            g = ph.temperature_array
+            x = MD.mean_free_path(ph, float(np.clip(np.mean(d['T']), g[0], g[-1]))).ravel()
+        else:
+            x = np.asarray(ph.omega, dtype=float).ravel()
+        km = np.nan_to_num(self.mode_k(d), nan=0.0, posinf=0.0, neginf=0.0)      # (a connection without a temperature difference)
+        grid = MD.accumulation_grid(x, points, log=(by == 'mfp'))
+        return dict(x=x, grid=grid, k=MD.accumulation(km, x, grid), k_mode=km, samples=d['samples'], step=d['step'])
+
+    def write_modes(self):
+        """k_accumulation.txt (by mean free path), k_accumulation_frequency.txt and mode_tally.npz, by rank 0."""
+        if self.modes_every <= 0:
+            return None
+        d = self.mode_distribution()                             # (all ranks: the read-out sums the accumulators over them)
+        if self.rank != 0 or not self.results_folder_name or d['samples'] == 0:
+            return None
+        folder, con = self.results_folder_name, self._geo.subvol_connections
+        for by in ('mfp', 'frequency'):
+            a = self.kappa_accumulation(by, dist=d)
+            MD.write_k_accumulation(MD.k_accumulation_path(folder, by), a['grid'], a['k'], con, by=by, steps=d['step'])
+        return MD.write_mode_tally(MD.mode_tally_path(folder), d['N'], d['E'], d['samples'], d['step'], self._ph.omega, self._ph.group_vel)
 
     # ----------------------------------------------------------------------------------- setup
     def _shard(self, n):
@@ -775,6 +854,8 @@ class Population(Constants):
             self.restart_reservoir_balance()
             if getattr(self, 'field_n', None) is not None:      # the field's window in progress no longer lines up: start again
                 self.engine.field(reset=True)
+            if getattr(self, 'modes_every', 0) > 0:             # ... and the mode tally's
+                self.engine.modes(reset=True)
 
     # ------------------------------------------------------------------------------- time loop
     def run_timestep(self, geometry, phonon):
@@ -798,6 +879,9 @@ class Population(Constants):
             field_on = getattr(self, 'field_n', None) is not None
             if field_on:                                        # ... and at the ends of the field's averaging windows
                 chunk = min(chunk, self.field_window - (self.current_timestep % self.field_window))
+            modes_on = getattr(self, 'modes_every', 0) > 0
+            if modes_on:                                        # ... and of the mode tally's
+                chunk = min(chunk, self.modes_window - (self.current_timestep % self.modes_window))
             # the reference grows its arrays as the ensemble grows; here the particle store is re-laid out with head room
             # before it can fill up (this rank's share of N_p against the engine's slots)
             # (the engine's slot count only changes when the store grows: asked for again after every 100 steps and after a reserve)
@@ -840,6 +924,8 @@ class Population(Constants):
             done += chunk
             if field_on and (self.current_timestep % self.field_window) == 0:
                 self._field_window_end()
+            if modes_on and (self.current_timestep % self.modes_window) == 0:
+                self._modes_window_end()
 
     def _every_hundred(self, geometry):
         if self.results_folder_name and getattr(self.args, 'checkpoint', True):     # every rank: its shard of the particles
@@ -849,6 +935,8 @@ class Population(Constants):
             self.write_k_contribution()
         if getattr(self, 'field_n', None) is not None and self.rank == 0:     # (the accumulator is the same on every rank)
             self.write_field()
+        if getattr(self, 'modes_every', 0) > 0:
+            self.write_modes()
         self.update_residue(geometry)
         info = 'Timestep {:>5d} - max residue: {:>9.3e} ({:<9s}) ['.format(int(self.current_timestep), self.max_residue, self.max_residue_qt)
         for sv in range(self.n_of_subvols):
