@@ -352,6 +352,47 @@ typedef struct {
 } nk_modes_report;
 int nk_modes_info(nk_ctx *ctx, nk_modes_report *out);
 
+/* Replica groups: R contexts that hold the same problem under different seeds (the runs behind an error bar) are stepped by
+ * shared launches -- per step ONE sweep and ONE tail launch for all of them instead of R of each, and one wait per call.  A
+ * workgroup of the shared launch finds its member and runs that member's step exactly as nk_step would: the rows and the
+ * particles of a member are the bits a solo run gives, whatever the group.  The fast path covers what one launch pair can
+ * express: tables in LDS (small meshes), no rough facets, no RBF temperatures, generators 'constant' / 'fixed_rate', one rank,
+ * bands / field / mode tally off; the resident kernel is never used for a group. */
+typedef struct nk_group nk_group;
+#define NK_GROUP_MAX_MEMBERS 32
+typedef struct {
+    int32_t R;                   /* members */
+    int32_t halted;              /* members whose store had to grow in the middle of a call, since nk_group_create */
+    int32_t finished_alone;      /* ... and that then finished the remaining steps of a call alone */
+    int32_t grid_sweep;          /* workgroups of the last k_sweep_group launch: the members' sweep grids, concatenated */
+    int32_t grid_tail;           /* ... and of the last k_tail_group launch: per member NB reduce workgroups + its emission's */
+    int32_t pad_;
+    int64_t steps;               /* steps taken through the group (every member took each of them) */
+    int64_t sweep_launches;      /* k_sweep_group launches issued */
+    int64_t tail_launches;       /* k_tail_group launches issued */
+    int64_t member_launches;     /* launches issued for ONE member: the preludes of contains_check steps (k_anchor, k_relax,
+                                  * k_contains), a first emission that no tail has run ahead, and the steps of stragglers
+                                  * (counted as 2 each) */
+    double sweep_kernel_ms;      /* mean duration of k_sweep_group, from HIP events on the first 4 steps of the last call of at */
+    double tail_kernel_ms;       /* least 4 steps (the convention of nk_timing); ... of k_tail_group */
+    double total_ms;             /* wall time of the last call's grouped steps on the stream */
+} nk_group_report;
+/* NK_ERR_ARG, with a reason that names the member (its index in `members`) and the condition, when R < 1 or R >
+ * NK_GROUP_MAX_MEMBERS, a context appears twice, the members are on different devices, a member is not ready (nk_step would
+ * refuse it) or outside the fast path, or the members disagree on what the shared launch bakes in: the kernel instantiation,
+ * S, R, NB, flux_every, contains_every, dt, the generator, the current step.  They may differ in seed, particles,
+ * temperatures and store size (hence in segments and in the LDS they need: a launch asks for the largest need, at most 64 KB).
+ * Nothing is launched then.  *out = NULL on failure; nk_group_last_error(NULL) has the reason. */
+int nk_group_create(nk_group **out, nk_ctx *const *members, int32_t R);
+void nk_group_destroy(nk_group *g);     /* never touches the members; destroy it before any member */
+/* nk_step(members[r], nsteps, &outs[r]) for every member; outs (or any of its entries' pointers) may be NULL.  A member whose
+ * store fills up stops on its own while the others run on; after the shared launches the host grows its store and finishes its
+ * remaining steps alone: nothing is dropped, every member has taken nsteps steps and delivered nsteps rows.  Between calls a
+ * member may be stepped alone with nk_step; NK_ERR_ARG when the members are then no longer at the same step. */
+int nk_group_step(nk_group *g, int32_t nsteps, nk_tally *outs /* [R] */);
+int nk_group_info(nk_group *g, nk_group_report *out);
+const char *nk_group_last_error(const nk_group *g);   /* g may be NULL: error of a failed nk_group_create */
+
 /* device versions of the reference's primitives, for parity tests (tests/ -m gpu) */
 int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
                      double *xc, double *tc, int32_t *fc);                       /* Mesh.py:806-856 */

@@ -60,6 +60,11 @@ def initialise_parser(debug_flag=False):
       help='[every]: tally energy and particle count per (subvolume, mode) every `every` steps (default 100, a multiple of '
            'n_dt_to_conv = 10) on the GPU over the convergence window, and write mode_tally.npz and the conductivity '
            'accumulated over the mean free path, k_accumulation.txt; 0 = off (the default)')
+    a('--replicas', default=[1], type=int, nargs=1,
+      help='R: run the same problem under the seeds seed, seed + 1, ..., seed + R - 1 (an error bar on the conductivity); '
+           'every replica writes its files to replica_<k> of the results folder, ensemble.txt holds the mean, the standard '
+           'deviation and the standard error over the replicas; where the configuration allows, all replicas advance by '
+           'shared GPU launches; 1 = a single run (the default)')
     return p
 
 

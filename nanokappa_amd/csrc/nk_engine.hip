@@ -21,6 +21,7 @@
 #include "nk_kernels.h"
 #include "nk_field.h"
 #include "nk_modes.h"
+#include "nk_group.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -2018,22 +2019,73 @@ static void nk_modes_transpose(const TI *in, TO *out, int M, int S) {
 // Enqueue up to `nsteps` timesteps without host synchronisation, drain the stream, copy the history rows back.  A sweep that
 // sees a segment which COULD overflow at the following step raises the halt word; the remaining steps of the batch then do
 // nothing, *done < nsteps comes back, and nk_step grows the store (state intact, nothing dropped) and carries on.
-static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
-    NkDev &d = ctx->d;
-    const int S = d.S, R = d.R, NB = d.NB;
-    const int HROW = NB + 2 * S + 8;
+// The parts of a batch that are a context's own business, shared by nk_step_batch and the grouped batch of a replica group
+// (nk_group_batch), so that a member of a group keeps exactly the state a solo run keeps.
+// The history rows live in pinned HOST memory that the device writes directly (1.1 KB per step over PCIe by the one
+// workgroup of the update): no copy back, no fill kernel -- a driver that steps one by one pays for every operation of a
+// call (round 3: fill + two copies = a tenth of such a call).
+static int nk_batch_hist(nk_ctx *ctx, int32_t nsteps) {
+    const int HROW = ctx->d.NB + 2 * ctx->d.S + 8;
     if (nsteps > ctx->hist_cap) {
         if (ctx->hist) hipHostFree(ctx->hist);
         ctx->hist = nullptr;
+        ctx->hist_cap = 0;
         const int rows_alloc = nsteps < 1024 ? 1024 : nsteps;   // generous: a later, longer call must not pay a realloc
-        // The history rows live in pinned HOST memory that the device writes directly (1.1 KB per step over PCIe by the one
-        // workgroup of the update): no copy back, no fill kernel -- a driver that steps one by one pays for every operation of a
-        // call (round 3: fill + two copies = a tenth of such a call).
         NK_HIP(hipHostMalloc((void **)&ctx->hist, (size_t)rows_alloc * HROW * sizeof(double), hipHostMallocMapped));
         ctx->hist_cap = rows_alloc;
     }
     ctx->timing.batches += 1;
     memset(ctx->hist, 0, (size_t)nsteps * HROW * sizeof(double));   // row_valid = 0 (host memory; the stream is idle between calls)
+    return NK_OK;
+}
+// What runs ahead of a contains_check step (every contains_every-th; nothing on the others): the segments moved down, the deferred
+// relaxation flushed (`pending` cleared, `flushed` set), k_contains.  *launches counts the kernels enqueued.
+static int nk_batch_prelude(nk_ctx *ctx, int64_t stepno, bool &pending, bool &flushed, int64_t *launches) {
+    NkDev &d = ctx->d;
+    if (!(ctx->params.contains_every > 0 && (stepno % ctx->params.contains_every) == 0 && d.nS > 0)) return NK_OK;
+    const bool anchors = ctx->walked && d.seg_lo;
+    { int rcn_ = nk_normalize(ctx, 1); if (rcn_) return rcn_; }       // (k_relax, k_contains: particles from slot 0)
+    int64_t n = anchors ? 1 : 0;
+    if (pending) {
+        k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 1);
+        pending = false;
+        flushed = true;
+        n += 1;
+    }
+    NK_GEOM_LAUNCH(k_contains, nk_sweep_grid(ctx), nk_lds(ctx, true), d, (uint32_t)stepno);
+    if (launches) *launches += n + 1;
+    return NK_OK;
+}
+// After the wait: the rows into h, the steps that ran, and the halt words as the last step that ran left them (its update wrote
+// them behind the row); no row: ask the device.
+static int nk_batch_collect(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
+    const NkDev &d = ctx->d;
+    const int S = d.S, NB = d.NB, HROW = NB + 2 * S + 8;
+    h.resize((size_t)nsteps * HROW);
+    memcpy(h.data(), ctx->hist, (size_t)nsteps * HROW * sizeof(double));
+    int32_t nd = 0;
+    while (nd < nsteps && h[(size_t)nd * HROW + NB + 2 * S + 1] != 0.0) ++nd;
+    if (nd > 0) for (int k_ = 0; k_ < 4; ++k_) ctx->halt_words[k_] = (int32_t)h[(size_t)(nd - 1) * HROW + NB + 2 * S + 4 + k_];
+    else NK_HIP(hipMemcpy(ctx->halt_words, d.halt, 16, hipMemcpyDeviceToHost));
+    *done = nd;
+    return NK_OK;
+}
+// How a batch of which nd steps ran leaves the emission that ran ahead and the deferred relaxation.
+static void nk_batch_leave(nk_ctx *ctx, int32_t nsteps, int32_t nd, bool tail_emit, bool relax0, bool flushed_first) {
+    // the emission that ran ahead in the last tail is good for the next call unless the batch halted (the store grows first)
+    const int32_t *hw_ = ctx->halt_words;
+    ctx->emitted_for = (tail_emit && nd == nsteps && !hw_[0] && !hw_[2] && !hw_[3]) ? ctx->step + nsteps : -1;
+    // the deferred relaxation as the device left it: pending after any completed step; if none ran, whatever it was before,
+    // unless a k_relax ahead of the first step flushed it (that kernel honours the halt word, which was clear then)
+    if (nd > 0) ctx->pending_relax = true;
+    else ctx->pending_relax = relax0 && !flushed_first;
+}
+
+static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
+    NkDev &d = ctx->d;
+    const int S = d.S, R = d.R, NB = d.NB;
+    const int HROW = NB + 2 * S + 8;
+    { int rch_ = nk_batch_hist(ctx, nsteps); if (rch_) return rch_; }
     const size_t lds_g = nk_lds(ctx, true), lds_w = nk_lds(ctx, true, d.pid ? 3 : 2), lds_e = nk_lds(ctx, true, 1);
     const int gm_ = nk_geom_mode(ctx);
     const bool rough_ = d.Fr > 0, rbf_ = d.sv_interp == 3, pid_ = (bool)d.pid, split_ = d.qx != nullptr;
@@ -2099,15 +2151,7 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     for (int s = 0; s < nsteps; ++s) {
         const int64_t stepno = ctx->step + s;
         const uint32_t step = (uint32_t)stepno;
-        if (ctx->params.contains_every > 0 && (stepno % ctx->params.contains_every) == 0 && d.nS > 0) {
-            { int rcn_ = nk_normalize(ctx, 1); if (rcn_) return rcn_; }       // (k_relax, k_contains: particles from slot 0)
-            if (pending) {
-                k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 1);
-                pending = false;
-                relax_flushed[(size_t)s] = 1;
-            }
-            NK_GEOM_LAUNCH(k_contains, nk_sweep_grid(ctx), lds_g, d, step);
-        }
+        { bool fl_ = false; int rcp_ = nk_batch_prelude(ctx, stepno, pending, fl_, nullptr); if (rcp_) return rcp_; if (fl_) relax_flushed[(size_t)s] = 1; }
         const int fe = ctx->params.flux_every;
         const int do_flux = (fe > 0 && ((stepno + 1) % fe) == 0) ? 1 : 0;
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s], ctx->stream));
@@ -2177,19 +2221,11 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     NK_HIP(hipGetLastError());
     // the history rows and the halt words come back through pinned memory, enqueued behind the steps: ONE wait per call (a
     // Population.run_timestep is one such call per step -- the reference driver's granularity, nanokappa.py:91-98)
-    const size_t hbytes = (size_t)nsteps * HROW * sizeof(double);
     // a call of a few steps (a driver that steps one by one) is over in a fraction of a millisecond: poll instead of sleeping on the
     // stream -- the wake-up of a blocked wait is a tenth of such a call
     if (nsteps <= 4) { hipError_t q_; while ((q_ = hipStreamQuery(ctx->stream)) == hipErrorNotReady) { } if (q_ != hipSuccess) { ctx->err = std::string("hipStreamQuery: ") + hipGetErrorString(q_); return NK_ERR_HIP; } }
     NK_HIP(hipStreamSynchronize(ctx->stream));
-    h.resize((size_t)nsteps * HROW);
-    memcpy(h.data(), ctx->hist, hbytes);
-    {   // the halt words as the last step that ran left them (its update wrote them behind the row); no row: ask the device
-        int last_ = -1;
-        for (int q_ = 0; q_ < nsteps && h[(size_t)q_ * HROW + NB + 2 * S + 1] != 0.0; ++q_) last_ = q_;
-        if (last_ >= 0) for (int k_ = 0; k_ < 4; ++k_) ctx->halt_words[k_] = (int32_t)h[(size_t)last_ * HROW + NB + 2 * S + 4 + k_];
-        else NK_HIP(hipMemcpy(ctx->halt_words, d.halt, 16, hipMemcpyDeviceToHost));
-    }
+    { int rcc_ = nk_batch_collect(ctx, nsteps, h, done); if (rcc_) return rcc_; }
 #ifdef NK_STAMPS
     if (d.stamps) {                                     // developer build: section shares of the LAST sweep of the batch
         std::vector<unsigned long long> st((size_t)d.nseg * 16);
@@ -2289,9 +2325,7 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
         }
     }
 #endif
-    int32_t nd = 0;
-    while (nd < nsteps && h[(size_t)nd * HROW + NB + 2 * S + 1] != 0.0) ++nd;
-    *done = nd;
+    const int32_t nd = *done;
     if (!band_s.empty()) {                                   // the band rows of the steps that ran
         const size_t rl = 4 * (size_t)S * ctx->band_B;
         std::vector<double> br(band_s.size() * rl);
@@ -2306,15 +2340,7 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
             ctx->band_steps.push_back(ctx->step + band_s[r]);
         }
     }
-    {   // the emission that ran ahead in the last tail is good for the next call unless the batch halted (the store grows first)
-        int32_t hw_[4];
-        memcpy(hw_, ctx->halt_words, 16);
-        ctx->emitted_for = (tail_emit && nd == nsteps && !hw_[0] && !hw_[2] && !hw_[3]) ? ctx->step + nsteps : -1;
-    }
-    // the deferred relaxation as the device left it: pending after any completed step; if none ran, whatever it was before,
-    // unless a k_relax ahead of the first step flushed it (that kernel honours the halt word, which was clear then)
-    if (nd > 0) ctx->pending_relax = true;
-    else ctx->pending_relax = relax0 && !(nsteps > 0 && relax_flushed[0]);
+    nk_batch_leave(ctx, nsteps, nd, tail_emit, relax0, nsteps > 0 && relax_flushed[0]);
     float ms = 0.f;
     double sk = 0.0, ek = 0.0, vk = 0.0;
     const int nt = nd < nev ? nd : nev;
@@ -2456,103 +2482,109 @@ static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h,
     return NK_OK;
 }
 
-int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
-    NK_ARG(ctx && nsteps > 0, "nk_step: bad arguments");
+// nk_step in three parts, shared with nk_group_step: what runs before the first batch of a call ...
+static int nk_step_begin(nk_ctx *ctx) {
     int rc = nk_check_ready(ctx);
     if (rc) return rc;
     NK_HIP(hipSetDevice(ctx->device));
     if ((rc = nk_update_tau_window(ctx, false))) return rc;
     if ((rc = nk_ensure_inbox(ctx))) return rc;
     if ((rc = nk_ensure_migration(ctx, 0))) return rc;
-    NkDev &d = ctx->d;
-    const int S = d.S, R = d.R, NB = d.NB;
-    const int HROW = NB + 2 * S + 8;
     ctx->stepped = true;
-    int32_t s_out = 0;                 // rows delivered so far
-    int overflow = 0;      // reason mask: 2 / 4 a segment filled up (tile commit / event survivors), 8 one_to_one inbox full,
-                           // 16 one_to_one index overflow
-    int grown = 0;
-    std::vector<double> h;
-    double last_T[2] = {0, 0};
     ctx->band_rows.clear();
     ctx->band_steps.clear();
     if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;
     if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;
-    while (s_out < nsteps) {
-        int32_t nd = 0;
-        if ((rc = nk_want_resident(ctx) ? nk_step_resident(ctx, nsteps - s_out, h, &nd) : nk_step_batch(ctx, nsteps - s_out, h, &nd))) return rc;
-        for (int s = 0; s < nd; ++s) {
-            const double *row = &h[(size_t)s * HROW];
-            if (row[NB + 2 * S + 3] != 0.0) overflow |= (int)row[NB + 2 * S + 3];
-            if (!out) continue;
-            const size_t q = (size_t)(s_out + s);
-            if (out->E_raw) memcpy(out->E_raw + q * S, row, S * 8);
-            if (out->N_sv) memcpy(out->N_sv + q * S, row + S, S * 8);
-            if (out->flux_raw) {
-                if (row[NB + 2 * S] != 0.0) memcpy(out->flux_raw + q * 3 * S, row + 2 * S, 3 * S * 8);
-                else for (int k = 0; k < 3 * S; ++k) out->flux_raw[q * 3 * S + k] = NAN;
-            }
-            if (out->N_leaving && R) memcpy(out->N_leaving + q * R, row + 5 * S, R * 8);
-            if (out->res_energy && R) memcpy(out->res_energy + q * R, row + 5 * S + R, R * 8);
-            if (out->res_flux && R) memcpy(out->res_flux + q * 3 * R, row + 5 * S + 2 * R, 3 * R * 8);
-            if (out->N_emitted) out->N_emitted[q] = row[NB - 1];
-            if (out->T_sv) memcpy(out->T_sv + q * S, row + NB, S * 8);
-            if (out->E_sv) memcpy(out->E_sv + q * S, row + NB + S, S * 8);
+    return NK_OK;
+}
+struct NkStepRun {
+    int32_t s_out = 0;     // rows delivered so far
+    int overflow = 0;      // reason mask: 2 / 4 a segment filled up (tile commit / event survivors), 8 one_to_one inbox full,
+                           // 16 one_to_one index overflow
+    int grown = 0;
+};
+// ... what follows every batch: the nd rows of `h` go to the caller's arrays, the context moves on by nd steps, and a batch that
+// halted is served (the store grows on the device, waiting migrants are delivered) ...
+static int nk_step_consume(nk_ctx *ctx, int32_t nsteps, nk_tally *out, NkStepRun &run, const std::vector<double> &h, int32_t nd) {
+    NkDev &d = ctx->d;
+    const int S = d.S, R = d.R, NB = d.NB;
+    const int HROW = NB + 2 * S + 8;
+    int rc = NK_OK;
+    for (int s = 0; s < nd; ++s) {
+        const double *row = &h[(size_t)s * HROW];
+        if (row[NB + 2 * S + 3] != 0.0) run.overflow |= (int)row[NB + 2 * S + 3];
+        if (!out) continue;
+        const size_t q = (size_t)(run.s_out + s);
+        if (out->E_raw) memcpy(out->E_raw + q * S, row, S * 8);
+        if (out->N_sv) memcpy(out->N_sv + q * S, row + S, S * 8);
+        if (out->flux_raw) {
+            if (row[NB + 2 * S] != 0.0) memcpy(out->flux_raw + q * 3 * S, row + 2 * S, 3 * S * 8);
+            else for (int k = 0; k < 3 * S; ++k) out->flux_raw[q * 3 * S + k] = NAN;
         }
-        if (nd > 0) {
-            const double *last = &h[(size_t)(nd - 1) * HROW];
-            nk_track_T(ctx, last + NB, S);
-            double live = 0.0;
-            for (int k = 0; k < S; ++k) live += last[S + k];
-            ctx->timing.live = (int64_t)live;
-            (void)last_T;
-        }
-        ctx->step += nd;
-        s_out += nd;
-        int32_t hw[4];
-        memcpy(hw, ctx->halt_words, 16);                 // as the batch left them (copied with the history rows)
-        if (s_out < nsteps || hw[0] || hw[2] || hw[3]) {
-            // halted: a segment could overflow at the next step (or could not take its migrants, which then wait in its
-            // inbox).  Grow every segment by half (on the device, state intact), deliver, and carry on.
-            ctx->timing.halts += 1;
-            if (++grown > 40) { ctx->err = "nk_step: the particle store keeps filling up"; return NK_ERR_CAPACITY; }
-            const bool only_inbox = hw[3] && !hw[0] && !hw[2] && s_out == nsteps;
-            if (!only_inbox) {
-                const int64_t need = (int64_t)d.segcap + d.segcap / 2 + 2 * nk_spawn_bound(ctx, d.nseg) + 2 * NK_TILE;
-                if ((rc = nk_regrow(ctx, need))) {
-                    ctx->err = "particle store nearly full after step " + std::to_string((long long)ctx->step) +
-                               " and it could not be grown (" + ctx->err + "); the state is intact";
-                    return NK_ERR_CAPACITY;
-                }
-            }
-            int32_t zero4[4] = {0, 0, 0, 0};
-            NK_HIP(hipMemcpy(d.halt, zero4, 16, hipMemcpyHostToDevice));
-            // (hw[2] comes out of the all-reduced vector: with several ranks every one of them is here at the same step, has
-            // grown its segments by the same amount, and delivers whatever waits in its own inboxes)
-            if (hw[2]) {                                 // migrants that did not fit: they do now
-                k_deliver<<<ctx->num_cu * 8, NK_WG, 0, ctx->stream>>>(d, 0);
-                NK_HIP(hipGetLastError());
-                NK_HIP(hipStreamSynchronize(ctx->stream));
-                int32_t again[4];
-                NK_HIP(hipMemcpy(again, d.halt, 16, hipMemcpyDeviceToHost));
-                if (again[2]) { ctx->err = "nk_step: migrating particles do not fit their segment after growing it"; return NK_ERR_CAPACITY; }
-                NK_HIP(hipMemcpy(d.halt, zero4, 16, hipMemcpyHostToDevice));
-            }
-            if (d.mig_buf && (hw[3] || !only_inbox)) {   // inboxes follow the segments (or double when they ran half full)
-                const int64_t want = std::max<int64_t>(hw[3] ? 2 * (int64_t)d.mig_cap : 0, d.segcap / 2);
-                if ((rc = nk_ensure_migration(ctx, want))) return rc;
-            }
-            if ((rc = nk_update_tau_window(ctx, false))) return rc;
-            if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;     // the store has grown: the field's scales follow
-            if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;     // ... and the mode tally's
-        }
+        if (out->N_leaving && R) memcpy(out->N_leaving + q * R, row + 5 * S, R * 8);
+        if (out->res_energy && R) memcpy(out->res_energy + q * R, row + 5 * S + R, R * 8);
+        if (out->res_flux && R) memcpy(out->res_flux + q * 3 * R, row + 5 * S + 2 * R, 3 * R * 8);
+        if (out->N_emitted) out->N_emitted[q] = row[NB - 1];
+        if (out->T_sv) memcpy(out->T_sv + q * S, row + NB, S * 8);
+        if (out->E_sv) memcpy(out->E_sv + q * S, row + NB + S, S * 8);
     }
-    ctx->timing.slots = d.cap;
+    if (nd > 0) {
+        const double *last = &h[(size_t)(nd - 1) * HROW];
+        nk_track_T(ctx, last + NB, S);
+        double live = 0.0;
+        for (int k = 0; k < S; ++k) live += last[S + k];
+        ctx->timing.live = (int64_t)live;
+    }
+    ctx->step += nd;
+    run.s_out += nd;
+    int32_t hw[4];
+    memcpy(hw, ctx->halt_words, 16);                 // as the batch left them (copied with the history rows)
+    if (run.s_out < nsteps || hw[0] || hw[2] || hw[3]) {
+        // halted: a segment could overflow at the next step (or could not take its migrants, which then wait in its
+        // inbox).  Grow every segment by half (on the device, state intact), deliver, and carry on.
+        ctx->timing.halts += 1;
+        if (++run.grown > 40) { ctx->err = "nk_step: the particle store keeps filling up"; return NK_ERR_CAPACITY; }
+        const bool only_inbox = hw[3] && !hw[0] && !hw[2] && run.s_out == nsteps;
+        if (!only_inbox) {
+            const int64_t need = (int64_t)d.segcap + d.segcap / 2 + 2 * nk_spawn_bound(ctx, d.nseg) + 2 * NK_TILE;
+            if ((rc = nk_regrow(ctx, need))) {
+                ctx->err = "particle store nearly full after step " + std::to_string((long long)ctx->step) +
+                           " and it could not be grown (" + ctx->err + "); the state is intact";
+                return NK_ERR_CAPACITY;
+            }
+        }
+        int32_t zero4[4] = {0, 0, 0, 0};
+        NK_HIP(hipMemcpy(d.halt, zero4, 16, hipMemcpyHostToDevice));
+        // (hw[2] comes out of the all-reduced vector: with several ranks every one of them is here at the same step, has
+        // grown its segments by the same amount, and delivers whatever waits in its own inboxes)
+        if (hw[2]) {                                 // migrants that did not fit: they do now
+            k_deliver<<<ctx->num_cu * 8, NK_WG, 0, ctx->stream>>>(d, 0);
+            NK_HIP(hipGetLastError());
+            NK_HIP(hipStreamSynchronize(ctx->stream));
+            int32_t again[4];
+            NK_HIP(hipMemcpy(again, d.halt, 16, hipMemcpyDeviceToHost));
+            if (again[2]) { ctx->err = "nk_step: migrating particles do not fit their segment after growing it"; return NK_ERR_CAPACITY; }
+            NK_HIP(hipMemcpy(d.halt, zero4, 16, hipMemcpyHostToDevice));
+        }
+        if (d.mig_buf && (hw[3] || !only_inbox)) {   // inboxes follow the segments (or double when they ran half full)
+            const int64_t want = std::max<int64_t>(hw[3] ? 2 * (int64_t)d.mig_cap : 0, d.segcap / 2);
+            if ((rc = nk_ensure_migration(ctx, want))) return rc;
+        }
+        if ((rc = nk_update_tau_window(ctx, false))) return rc;
+        if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;     // the store has grown: the field's scales follow
+        if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;     // ... and the mode tally's
+    }
+    return NK_OK;
+}
+// ... and what ends the call
+static int nk_step_end(nk_ctx *ctx, int overflow) {
+    int rc = NK_OK;
+    ctx->timing.slots = ctx->d.cap;
     if (overflow & 256) {                                // k_resident: its grid barrier was not met (a workgroup was not resident?)
         uint32_t z2[2] = {0u, 0u};
         NK_HIP(hipMemcpy(ctx->anomalies + 1, z2, 8, hipMemcpyHostToDevice));
         int32_t z = 0;
-        NK_HIP(hipMemcpy(d.overflow, &z, 4, hipMemcpyHostToDevice));
+        NK_HIP(hipMemcpy(ctx->d.overflow, &z, 4, hipMemcpyHostToDevice));
         ctx->err = "nk_step: the resident kernel's grid barrier timed out; set NK_NO_RESIDENT=1";
         return NK_ERR_HIP;
     }
@@ -2573,6 +2605,381 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
         if ((rc = nk_modes_status(ctx, st, "nk_step"))) return rc;
     }
     return NK_OK;
+}
+
+int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
+    NK_ARG(ctx && nsteps > 0, "nk_step: bad arguments");
+    int rc = nk_step_begin(ctx);
+    if (rc) return rc;
+    NkStepRun run;
+    std::vector<double> h;
+    while (run.s_out < nsteps) {
+        int32_t nd = 0;
+        if ((rc = nk_want_resident(ctx) ? nk_step_resident(ctx, nsteps - run.s_out, h, &nd) : nk_step_batch(ctx, nsteps - run.s_out, h, &nd))) return rc;
+        if ((rc = nk_step_consume(ctx, nsteps, out, run, h, nd))) return rc;
+    }
+    return nk_step_end(ctx, run.overflow);
+}
+
+// =============================================================================== replica groups
+// R contexts with the same configuration stepped by shared launches (k_sweep_group / k_tail_group, nk_group.hip).  The group owns
+// a device copy of the members' NkDevs (refreshed once per call: the lifetime window or a grown store change them), the prefix
+// tables of the two grids, and one record per (step, member) of a call; everything else -- particles, tables, tallies, history
+// rows, halt words, the alternating walk, the emission that ran ahead, the deferred relaxation -- stays the member's own and is
+// kept exactly as nk_step_batch keeps it, so that a member can be stepped alone between group calls.
+struct nk_group {
+    int R = 0;
+    std::vector<nk_ctx *> m;
+    int device = 0;
+    std::string err;
+    unsigned char *dev = nullptr;          // NkGroupHead, then NkDev[R]
+    unsigned char *stage = nullptr;        // pinned host copy of the same
+    NkGroupRec *recs_d = nullptr, *recs_h = nullptr;   // [recs_cap steps][R]; recs_h pinned
+    int recs_cap = 0;
+    std::vector<hipEvent_t> ev;            // 3 per timed step (4 steps), then the call's first and last
+    std::vector<char> halted, alone;       // per member: it has halted / finished a call alone since the group was created
+    nk_group_report rep = {};
+};
+static thread_local std::string g_group_error;
+
+#define NK_GHIP(call)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) {                                                                        \
+            g->err = std::string(#call) + ": " + hipGetErrorString(e_);                                \
+            return NK_ERR_HIP;                                                                         \
+        }                                                                                              \
+    } while (0)
+
+// what the shared launches bake in: the members of a group agree on all of it
+struct NkGroupKey {
+    NkGroupKind kind;
+    int S, R, NB, flux_every, contains_every, res_gen;
+    double dt;
+    int64_t step;
+};
+static NkGroupKey nk_group_key(nk_ctx *ctx) {
+    const NkDev &d = ctx->d;
+    NkGroupKey k;
+    k.kind.pid = (bool)d.pid;
+    k.kind.lrec = nk_want_lrec(ctx);
+    k.kind.fast = k.kind.pid ? 0 : nk_sweep_fast(ctx);
+    k.kind.box = d.box != 0;
+    k.S = d.S; k.R = d.R; k.NB = d.NB;
+    k.flux_every = ctx->params.flux_every; k.contains_every = ctx->params.contains_every; k.res_gen = d.res_gen;
+    k.dt = d.dt;
+    k.step = ctx->step;
+    return k;
+}
+// What a group call is launched with: the members' common key and the largest LDS need among them (the LDS a member needs follows
+// its segmentation -- the mode records of a segment -- hence its store size, in which members may differ: a launch asks for the
+// largest need, every workgroup carves its own member's layout out of it).  Worked out once per call by nk_group_check.
+struct NkGroupPlan { NkGroupKey key; size_t lds_w = 0, lds_t = 0; int device = 0; };
+// "" when the member is inside the fast path's scope, else the reason
+static std::string nk_group_scope(nk_ctx *ctx) {
+    const NkDev &d = ctx->d;
+    if (!(ctx->have_material && ctx->have_mesh && ctx->have_sv && ctx->have_params)) return "it is not ready (engine not configured: need material, mesh, subvolumes and params)";
+    if (ctx->comm || d.nranks != 1) return "it belongs to a communicator (several ranks)";
+    if (d.Fr > 0 || d.mig_buf) return "it has rough facets (their migrants are delivered between the sweep and the tail)";
+    if (nk_geom_mode(ctx) != 1) return "its mesh is too large for tables in LDS";
+    if (nk_want_split(ctx) || d.qx) return "it uses the split sweep";
+    if (d.sv_interp == 3) return "it uses RBF temperatures";
+    if (d.res_gen == 2) return "its generator is 'one_to_one'";
+    if (ctx->band_B > 0) return "its band-resolved flux is on (nk_set_bands)";
+    if (ctx->field.on) return "its field maps are on (nk_set_field)";
+    if (ctx->modes.on) return "its mode tally is on (nk_set_modes)";
+    if (d.R > 0 && getenv("NK_NO_TAIL_EMIT")) return "NK_NO_TAIL_EMIT is set (the emission would need a launch of its own)";
+    return "";
+}
+// Everything nk_group_create refuses, also asked again by every nk_group_step (members may have been stepped alone or re-configured).
+static int nk_group_check(nk_ctx *const *m, int R, NkGroupPlan *plan, std::string &err) {
+    if (R < 1 || R > NK_GROUP_MAX_MEMBERS) { err = "nk_group: R = " + std::to_string(R) + " is outside 1 .. " + std::to_string(NK_GROUP_MAX_MEMBERS); return NK_ERR_ARG; }
+    if (!m) { err = "nk_group: NULL members"; return NK_ERR_ARG; }
+    for (int r = 0; r < R; ++r) {
+        if (!m[r]) { err = "nk_group: member " + std::to_string(r) + " is NULL"; return NK_ERR_ARG; }
+        for (int q = 0; q < r; ++q)
+            if (m[q] == m[r]) { err = "nk_group: member " + std::to_string(r) + " is the same context as member " + std::to_string(q) + " (given twice)"; return NK_ERR_ARG; }
+    }
+    for (int r = 1; r < R; ++r)
+        if (m[r]->device != m[0]->device) {
+            err = "nk_group: member " + std::to_string(r) + " is on device " + std::to_string(m[r]->device) + ", member 0 on device " + std::to_string(m[0]->device);
+            return NK_ERR_ARG;
+        }
+    for (int r = 0; r < R; ++r) {
+        const std::string why = nk_group_scope(m[r]);
+        if (!why.empty()) { err = "nk_group: member " + std::to_string(r) + " is outside the grouped path: " + why; return NK_ERR_ARG; }
+    }
+    for (int r = 0; r < R; ++r) {                        // (may re-deal a store whose layout no longer fits the configuration, as nk_step would)
+        if (nk_check_ready(m[r])) { err = "nk_group: member " + std::to_string(r) + " is not ready: " + m[r]->err; return NK_ERR_ARG; }
+        const std::string why = nk_group_scope(m[r]);
+        if (!why.empty()) { err = "nk_group: member " + std::to_string(r) + " is outside the grouped path: " + why; return NK_ERR_ARG; }
+    }
+    size_t lds_w = 0, lds_t = 0;
+    for (int r = 0; r < R; ++r) {
+        const size_t w = nk_lds(m[r], true, m[r]->d.pid ? 3 : 2), e = nk_lds(m[r], true, 1);
+        const size_t tl = e > (size_t)(NK_WG * 8 + 16) ? e : (size_t)(NK_WG * 8 + 16);          // (k_tail: the emission's tables or the reduce's scratch)
+        if (w > 64 * 1024 || tl > 64 * 1024) { err = "nk_group: member " + std::to_string(r) + " is outside the grouped path: its tables need more than 64 KB of LDS"; return NK_ERR_ARG; }
+        lds_w = std::max(lds_w, w); lds_t = std::max(lds_t, tl);
+    }
+    const NkGroupKey k0 = nk_group_key(m[0]);
+    for (int r = 1; r < R; ++r) {
+        const NkGroupKey k = nk_group_key(m[r]);
+        const char *what = nullptr;
+        std::string a, b;
+#define NK_GROUP_SAME(field, name) if (!what && !(k.field == k0.field)) { what = name; a = std::to_string(k.field); b = std::to_string(k0.field); }
+        NK_GROUP_SAME(step, "current step")
+        NK_GROUP_SAME(S, "subvolumes")
+        NK_GROUP_SAME(R, "reservoirs")
+        NK_GROUP_SAME(NB, "tally bins")
+        NK_GROUP_SAME(flux_every, "flux_every")
+        NK_GROUP_SAME(contains_every, "contains_every")
+        NK_GROUP_SAME(dt, "dt")
+        NK_GROUP_SAME(res_gen, "generator")
+        NK_GROUP_SAME(kind.pid, "kernel instantiation (particle ids)")
+        NK_GROUP_SAME(kind.lrec, "kernel instantiation (mode records in LDS)")
+        NK_GROUP_SAME(kind.fast, "kernel instantiation (subvolume fast path)")
+        NK_GROUP_SAME(kind.box, "kernel instantiation (box store)")
+#undef NK_GROUP_SAME
+        if (what) {
+            err = "nk_group: member " + std::to_string(r) + " disagrees with member 0 on the " + what + " (" + a + " against " + b + ")";
+            return NK_ERR_ARG;
+        }
+    }
+    if (plan) { plan->key = k0; plan->lds_w = lds_w; plan->lds_t = lds_t; plan->device = m[0]->device; }
+    return NK_OK;
+}
+
+int nk_group_create(nk_group **out, nk_ctx *const *members, int32_t R) {
+    if (!out) { g_group_error = "nk_group_create: NULL out"; return NK_ERR_ARG; }
+    *out = nullptr;
+    NkGroupPlan plan;
+    int rc = nk_group_check(members, R, &plan, g_group_error);
+    if (rc) return rc;
+    const int device = plan.device;
+    nk_group *g = new nk_group();
+    g->R = R;
+    g->m.assign(members, members + R);
+    g->halted.assign((size_t)R, 0);
+    g->alone.assign((size_t)R, 0);
+    g->device = device;
+    g->rep.R = R;
+    const size_t bytes = sizeof(NkGroupHead) + (size_t)NK_GROUP_MAX * sizeof(NkDev);
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc((void **)&g->dev, bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&g->stage, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) {
+        g->ev.resize(3 * 4 + 2);
+        for (auto &v : g->ev) { v = nullptr; if (e == hipSuccess) e = hipEventCreate(&v); }
+    }
+    if (e != hipSuccess) {
+        g_group_error = std::string("nk_group_create: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+        nk_group_destroy(g);
+        return NK_ERR_HIP;
+    }
+    *out = g;
+    return NK_OK;
+}
+
+void nk_group_destroy(nk_group *g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    for (auto &v : g->ev) if (v) hipEventDestroy(v);
+    if (g->dev) hipFree(g->dev);
+    if (g->stage) hipHostFree(g->stage);
+    if (g->recs_d) hipFree(g->recs_d);
+    if (g->recs_h) hipHostFree(g->recs_h);
+    delete g;
+}
+
+const char *nk_group_last_error(const nk_group *g) { return g ? g->err.c_str() : g_group_error.c_str(); }
+
+int nk_group_info(nk_group *g, nk_group_report *out) {
+    if (!g || !out) { if (g) g->err = "nk_group_info: NULL argument"; return NK_ERR_ARG; }
+    *out = g->rep;
+    return NK_OK;
+}
+
+// nk_step_batch for all members at once, within the grouped path's scope (nk_group_scope): per step one k_sweep_group and one
+// k_tail_group on `stream` (every member's ctx->stream is that stream during the call), one wait for the whole call.  hs[r] / nds[r]:
+// member r's history rows and how many of its steps ran (a member that halted stops alone).
+static int nk_group_batch(nk_group *g, const NkGroupPlan &plan, hipStream_t stream, int32_t nsteps, std::vector<std::vector<double>> &hs,
+                          std::vector<int32_t> &nds) {
+    const int R = g->R;
+    const NkGroupKey &key = plan.key;
+    const size_t lds_w = plan.lds_w, lds_t = plan.lds_t;
+    const int S = key.S, NB = key.NB, HROW = NB + 2 * S + 8;
+    NkGroupHead *head = reinterpret_cast<NkGroupHead *>(g->stage);
+    NkDev *devs = reinterpret_cast<NkDev *>(g->stage + sizeof(NkGroupHead));
+    for (int k = 0; k <= NK_GROUP_MAX; ++k) head->pre_sweep[k] = head->pre_tail[k] = INT32_MAX;
+    for (int k = 0; k < NK_GROUP_MAX; ++k) head->rows[k] = 0;
+    head->NB = NB; head->pad_ = 0;
+    if (nsteps > g->recs_cap) {
+        if (g->recs_d) hipFree(g->recs_d);
+        if (g->recs_h) hipHostFree(g->recs_h);
+        g->recs_d = g->recs_h = nullptr; g->recs_cap = 0;
+        const int cap = nsteps < 1024 ? 1024 : nsteps;
+        NK_GHIP(hipMalloc((void **)&g->recs_d, (size_t)cap * R * sizeof(NkGroupRec)));
+        NK_GHIP(hipHostMalloc((void **)&g->recs_h, (size_t)cap * R * sizeof(NkGroupRec), hipHostMallocDefault));
+        g->recs_cap = cap;
+    }
+    struct Member { int g_sweep = 0, g_emit = 0; bool alt = false, pending = false, relax0 = false, flushed0 = false, emitted_ahead = false, tail_emit = false; };
+    std::vector<Member> mem((size_t)R);
+    int grid_sweep = 0, grid_tail = 0;
+    for (int r = 0; r < R; ++r) {
+        nk_ctx *ctx = g->m[r];
+        NkDev &d = ctx->d;
+        Member &me = mem[(size_t)r];
+        if (nk_batch_hist(ctx, nsteps)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
+        (void)nk_sweep_blocks(ctx);
+        me.g_sweep = ctx->g_sweep < (d.nseg + 3) / 4 ? ctx->g_sweep : (d.nseg + 3) / 4;
+        me.tail_emit = d.R > 0;                          // (not 'one_to_one', NK_NO_TAIL_EMIT unset: nk_group_scope)
+        me.g_emit = me.tail_emit ? (ctx->num_cu * 8 < (d.nseg + 3) / 4 ? ctx->num_cu * 8 : (d.nseg + 3) / 4) : 0;
+        d.tree_lds_fam0 = d.tree_nfam; d.tree_lds_off = 0;
+        me.relax0 = me.pending = ctx->pending_relax;
+        me.emitted_ahead = me.tail_emit && ctx->emitted_for == ctx->step;
+        ctx->emitted_for = -1;
+        ctx->timing.emit_fused = me.tail_emit ? 1 : 0;
+        me.alt = d.seg_lo && !getenv("NK_NO_ALTERNATE");
+        if (!me.alt) {
+            const bool launches = ctx->walked && d.seg_lo;
+            if (nk_normalize(ctx)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
+            if (launches) g->rep.member_launches += 1;
+        }
+        d.down = 0;
+        head->pre_sweep[r] = grid_sweep; head->pre_tail[r] = grid_tail; head->rows[r] = me.g_sweep;
+        grid_sweep += me.g_sweep;
+        grid_tail += NB + me.g_emit;
+        devs[r] = d;
+    }
+    head->pre_sweep[R] = grid_sweep; head->pre_tail[R] = grid_tail;
+    // the records of the whole call: what nk_step_batch passes to each step's launches
+    for (int r = 0; r < R; ++r) {
+        nk_ctx *ctx = g->m[r];
+        const NkDev &d = ctx->d;
+        bool pending = mem[(size_t)r].pending;
+        for (int s = 0; s < nsteps; ++s) {
+            const int64_t stepno = ctx->step + s;
+            if (key.contains_every > 0 && (stepno % key.contains_every) == 0 && d.nS > 0) pending = false;   // (k_relax runs ahead of k_contains)
+            NkGroupRec &rec = g->recs_h[(size_t)s * R + r];
+            rec.step = (uint32_t)stepno;
+            rec.do_relax = pending ? 1 : 0;
+            rec.do_flux = (key.flux_every > 0 && ((stepno + 1) % key.flux_every) == 0) ? 1 : 0;
+            rec.down = mem[(size_t)r].alt ? (int32_t)(stepno & 1) : 0;
+            rec.hist_row = ctx->hist + (size_t)s * HROW;
+            rec.acc = ctx->acc;
+            pending = true;
+        }
+    }
+    NkGroupHead *head_d = reinterpret_cast<NkGroupHead *>(g->dev);
+    NkDev *devs_d = reinterpret_cast<NkDev *>(g->dev + sizeof(NkGroupHead));
+    NK_GHIP(hipMemcpyAsync(g->dev, g->stage, sizeof(NkGroupHead) + (size_t)R * sizeof(NkDev), hipMemcpyHostToDevice, stream));
+    NK_GHIP(hipMemcpyAsync(g->recs_d, g->recs_h, (size_t)nsteps * R * sizeof(NkGroupRec), hipMemcpyHostToDevice, stream));
+    const int nev = nsteps < 4 ? 0 : 4;                  // (nk_timing's convention: none for the short calls of a driver that steps one by one)
+    hipEvent_t *ev = g->ev.data();
+    hipEvent_t t0 = g->ev[12], t1 = g->ev[13];
+    NK_GHIP(hipEventRecord(t0, stream));
+    for (int s = 0; s < nsteps; ++s) {
+        for (int r = 0; r < R; ++r) {                    // what a step may need per member: the prelude of a contains_check step ...
+            nk_ctx *ctx = g->m[r];
+            NkDev &d = ctx->d;
+            Member &me = mem[(size_t)r];
+            const int64_t stepno = ctx->step + s;
+            {
+                bool fl_ = false;
+                if (nk_batch_prelude(ctx, stepno, me.pending, fl_, &g->rep.member_launches)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
+                if (fl_ && s == 0) me.flushed0 = true;
+            }
+            // ... and an emission that no tail has run ahead (the first step after anything that changed the store or the tables)
+            if (d.R > 0 && !me.emitted_ahead) {
+                NK_EMIT_LAUNCH(k_emit, me.g_emit, nk_lds(ctx, true, 1), d, (uint32_t)stepno);
+                g->rep.member_launches += 1;
+            }
+            if (me.alt) ctx->walked = true;
+            me.emitted_ahead = me.tail_emit;
+            me.pending = true;
+        }
+        if (s < nev) NK_GHIP(hipEventRecord(ev[3 * s], stream));
+        NK_GHIP(nk_group_launch_sweep(key.kind, grid_sweep, lds_w, stream, head_d, devs_d, g->recs_d + (size_t)s * R));
+        if (s < nev) NK_GHIP(hipEventRecord(ev[3 * s + 1], stream));
+        NK_GHIP(nk_group_launch_tail(key.kind.box, grid_tail, lds_t, stream, head_d, devs_d, g->recs_d + (size_t)s * R));
+        if (s < nev) NK_GHIP(hipEventRecord(ev[3 * s + 2], stream));
+        g->rep.sweep_launches += 1;
+        g->rep.tail_launches += 1;
+    }
+    NK_GHIP(hipEventRecord(t1, stream));
+    NK_GHIP(hipGetLastError());
+    g->rep.grid_sweep = grid_sweep;
+    g->rep.grid_tail = grid_tail;
+    // ONE wait per call; a call of a few steps polls instead of sleeping on the stream (nk_step_batch)
+    if (nsteps <= 4) { hipError_t q_; while ((q_ = hipStreamQuery(stream)) == hipErrorNotReady) { } if (q_ != hipSuccess) { g->err = std::string("hipStreamQuery: ") + hipGetErrorString(q_); return NK_ERR_HIP; } }
+    NK_GHIP(hipStreamSynchronize(stream));
+    bool all_ran = true;
+    for (int r = 0; r < R; ++r) {
+        nk_ctx *ctx = g->m[r];
+        const Member &me = mem[(size_t)r];
+        int32_t nd = 0;
+        if (nk_batch_collect(ctx, nsteps, hs[(size_t)r], &nd)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
+        nds[(size_t)r] = nd;
+        nk_batch_leave(ctx, nsteps, nd, me.tail_emit, me.relax0, me.flushed0);
+        if (nd < nsteps) all_ran = false;
+    }
+    float ms = 0.f;
+    if (nev > 0 && all_ran) {
+        double sk = 0.0, tk = 0.0;
+        for (int s = 0; s < nev; ++s) {
+            NK_GHIP(hipEventElapsedTime(&ms, ev[3 * s], ev[3 * s + 1])); sk += ms;
+            NK_GHIP(hipEventElapsedTime(&ms, ev[3 * s + 1], ev[3 * s + 2])); tk += ms;
+        }
+        g->rep.sweep_kernel_ms = sk / nev;
+        g->rep.tail_kernel_ms = tk / nev;
+    }
+    NK_GHIP(hipEventElapsedTime(&ms, t0, t1));
+    g->rep.total_ms = ms;
+    return NK_OK;
+}
+
+int nk_group_step(nk_group *g, int32_t nsteps, nk_tally *outs) {
+    if (!g) return NK_ERR_ARG;
+    if (nsteps <= 0) { g->err = "nk_group_step: bad arguments"; return NK_ERR_ARG; }
+    const int R = g->R;
+    NkGroupPlan plan;
+    int rc = nk_group_check(g->m.data(), R, &plan, g->err);
+    if (rc) return rc;
+    NK_GHIP(hipSetDevice(g->device));
+    // one stream for the whole call: member 0's.  The members' own streams are idle between calls (every call ends with a wait).
+    const hipStream_t stream = g->m[0]->stream;
+    std::vector<hipStream_t> own((size_t)R);
+    for (int r = 0; r < R; ++r) { own[(size_t)r] = g->m[r]->stream; g->m[r]->stream = stream; }
+    auto leave = [&](int code) { for (int r = 0; r < R; ++r) g->m[r]->stream = own[(size_t)r]; return code; };
+    for (int r = 0; r < R; ++r)
+        if ((rc = nk_step_begin(g->m[r]))) { g->err = "member " + std::to_string(r) + ": " + g->m[r]->err; return leave(rc); }
+    std::vector<std::vector<double>> hs((size_t)R);
+    std::vector<int32_t> nds((size_t)R, 0);
+    if ((rc = nk_group_batch(g, plan, stream, nsteps, hs, nds))) return leave(rc);
+    g->rep.steps += nsteps;
+    for (int r = 0; r < R; ++r) {
+        nk_ctx *ctx = g->m[r];
+        NkStepRun run;
+        nk_tally *out = outs ? &outs[r] : nullptr;
+        const int64_t halts0 = ctx->timing.halts;
+        if ((rc = nk_step_consume(ctx, nsteps, out, run, hs[(size_t)r], nds[(size_t)r]))) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return leave(rc); }
+        if (ctx->timing.halts != halts0 && !g->halted[(size_t)r]) { g->halted[(size_t)r] = 1; g->rep.halted += 1; }
+        if (run.s_out < nsteps) {                        // a straggler: its store has grown, it takes its remaining steps alone
+            if (!g->alone[(size_t)r]) { g->alone[(size_t)r] = 1; g->rep.finished_alone += 1; }
+            std::vector<double> h;
+            while (run.s_out < nsteps) {
+                int32_t nd = 0;
+                if ((rc = nk_step_batch(ctx, nsteps - run.s_out, h, &nd)) || (rc = nk_step_consume(ctx, nsteps, out, run, h, nd))) {
+                    g->err = "member " + std::to_string(r) + ": " + ctx->err;
+                    return leave(rc);
+                }
+                g->rep.member_launches += 2 * (int64_t)nd;
+            }
+        }
+        if ((rc = nk_step_end(ctx, run.overflow))) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return leave(rc); }
+    }
+    return leave(NK_OK);
 }
 
 int nk_download_particles(nk_ctx *ctx, int64_t capacity, double *x, double *y, double *z, int32_t *mode, double *occ,

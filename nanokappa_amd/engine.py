@@ -89,7 +89,8 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
            'nk_tally_bands_state', 'nk_set_field', 'nk_get_field', 'nk_tally_field_state', 'nk_field_info',
-           'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info']
+           'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
+           'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -111,6 +112,15 @@ class nk_modes_report(C.Structure):
                 ('owner_path', C.c_int32), ('on', C.c_int32)]
 
 
+class nk_group_report(C.Structure):
+    _fields_ = [('R', C.c_int32), ('halted', C.c_int32), ('finished_alone', C.c_int32), ('grid_sweep', C.c_int32),
+                ('grid_tail', C.c_int32), ('pad_', C.c_int32), ('steps', C.c_int64), ('sweep_launches', C.c_int64),
+                ('tail_launches', C.c_int64), ('member_launches', C.c_int64), ('sweep_kernel_ms', C.c_double),
+                ('tail_kernel_ms', C.c_double), ('total_ms', C.c_double)]
+
+
+ERR_ARG = -2                 # NK_ERR_ARG (include/nanokappa_hip.h)
+GROUP_MAX_MEMBERS = 32       # NK_GROUP_MAX_MEMBERS
 MODES_GLOBAL = 1             # nk_set_modes flags (include/nanokappa_hip.h)
 MODES_TEST_SMALL_BOUND = 2
 FIELD_GLOBAL = 1             # nk_set_field flags (include/nanokappa_hip.h)
@@ -183,6 +193,13 @@ def load_library():
     L.nk_get_modes.argtypes = [C.c_void_p, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
     L.nk_tally_modes_state.argtypes = [C.c_void_p, c_i64p, c_i64p]
     L.nk_modes_info.argtypes = [C.c_void_p, C.POINTER(nk_modes_report)]
+    L.nk_group_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32]
+    L.nk_group_destroy.argtypes = [C.c_void_p]
+    L.nk_group_destroy.restype = None
+    L.nk_group_step.argtypes = [C.c_void_p, C.c_int32, C.POINTER(nk_tally)]
+    L.nk_group_info.argtypes = [C.c_void_p, C.POINTER(nk_group_report)]
+    L.nk_group_last_error.restype = C.c_char_p
+    L.nk_group_last_error.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -408,9 +425,8 @@ class Engine(object):
         self._ck(self.L.nk_tally_state(self.h, E.ctypes.data_as(c_dp), N.ctypes.data_as(c_dp), F.ctypes.data_as(c_dp)), 'nk_tally_state')
         return E, N, F
 
-    def step(self, nsteps=1):
-        """Run nsteps timesteps; returns a dict of per-step arrays (see nk_tally in the header).  The arrays are views of ONE block
-        (a driver that steps one by one calls this a thousand times a second: one allocation and one address instead of nine)."""
+    def _tally_block(self, nsteps):
+        """The dict of per-step arrays step() returns (views of ONE block) and the nk_tally that points into it."""
         S, R = self.S, max(self.R, 0)
         shapes = (('T_sv', (nsteps, S)), ('E_sv', (nsteps, S)), ('E_raw', (nsteps, S)), ('N_sv', (nsteps, S)), ('flux_raw', (nsteps, S, 3)),
                   ('N_leaving', (nsteps, R)), ('res_energy', (nsteps, R)), ('res_flux', (nsteps, R, 3)), ('N_emitted', (nsteps,)))
@@ -423,6 +439,12 @@ class Engine(object):
             out[k] = block[off:off + n].reshape(shp)
             setattr(t, k, C.cast(base + 8 * off, c_dp))
             off += n
+        return out, t
+
+    def step(self, nsteps=1):
+        """Run nsteps timesteps; returns a dict of per-step arrays (see nk_tally in the header).  The arrays are views of ONE block
+        (a driver that steps one by one calls this a thousand times a second: one allocation and one address instead of nine)."""
+        out, t = self._tally_block(nsteps)
         self._ck(self.L.nk_step(self.h, int(nsteps), C.byref(t)), 'nk_step')
         if self.nbands > 0:
             out['band_F'], out['band_N'], out['band_steps'] = self._band_rows()
@@ -742,3 +764,52 @@ class Engine(object):
         if rc != 0:
             raise NkError('nk_uniform2 failed')
         return u0.value, u1.value
+
+
+class EngineGroup(object):
+    """One nk_group: engines that hold the same problem under different seeds, stepped by shared launches (one sweep and one
+    tail launch per step for all of them).  Raises NkError (its `code` is ERR_ARG; the message names the member and the reason) when the
+    engines cannot be grouped; the engines themselves stay usable, before, between and after group calls."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)             # kept alive: the group must be destroyed before any member
+        self.L = load_library()
+        self.h = None
+        n = len(self.engines)
+        arr = (C.c_void_p * max(n, 1))(*[e.h for e in self.engines])
+        h = C.c_void_p()
+        rc = self.L.nk_group_create(C.byref(h), arr, n)
+        if rc != 0:
+            err = NkError('nk_group_create failed (%d): %s' % (rc, self.L.nk_group_last_error(None).decode()))
+            err.code = rc
+            raise err
+        self.h = h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.L.nk_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, nsteps=1):
+        """nsteps timesteps of every member; a list of the dicts Engine.step returns, one per member."""
+        blocks = [e._tally_block(nsteps) for e in self.engines]
+        ts = (nk_tally * len(blocks))(*[t for _, t in blocks])
+        rc = self.L.nk_group_step(self.h, int(nsteps), ts)
+        if rc != 0:
+            err = NkError('nk_group_step failed (%d): %s' % (rc, self.L.nk_group_last_error(self.h).decode()))
+            err.code = rc
+            raise err
+        return [out for out, _ in blocks]
+
+    def info(self):
+        r = nk_group_report()
+        rc = self.L.nk_group_info(self.h, C.byref(r))
+        if rc != 0:
+            raise NkError('nk_group_info failed (%d)' % rc)
+        return {k: getattr(r, k) for k, _ in nk_group_report._fields_ if k != 'pad_'}

@@ -14,6 +14,27 @@ from .phonon import Phonon
 from .population import Population
 
 
+def run_replicas(args, geo, phonons, replicas, start, max_time):
+    """--replicas R > 1: the time loop of main() for an Ensemble of R populations (seeds seed .. seed + R - 1)."""
+    from .ensemble import Ensemble, replica_seeds
+    ens = Ensemble(args, geo, phonons, replica_seeds(args.seed, replicas))
+    flag = True
+    while flag:
+        n = min(100 - ens.current_timestep % 100, args.iterations[0] - ens.current_timestep)
+        ens.run(max(n, 1))
+        flag = (ens.current_timestep < args.iterations[0]) and not ens.finish_sim
+        if max_time.total_seconds() > 0:
+            flag = flag and datetime.now() - start < max_time
+    print('Saving end of run particle data...')
+    ens.write_final_state()
+    s = ens.write_summary()
+    for name in ('kappa', 'con_k'):
+        if name in s:
+            print('%s over %d replicas: mean %s  std %s  standard error %s' % (name, replicas, s[name]['mean'], s[name]['std'], s[name]['sem']))
+    ens.close()
+    return ens
+
+
 def main(argv=None):
     args = read_args(False, argv)
     args = generate_results_folder(args)
@@ -33,6 +54,16 @@ def main(argv=None):
     print('Simulation name: %s' % args.results_folder)
     geo = Geometry(args)
     phonons = Phonon(args, 0)
+    replicas = int(getattr(args, 'replicas', [1])[0])
+    if replicas < 1:
+        raise SystemExit('--replicas must be at least 1')
+    if replicas > 1:
+        ens = run_replicas(args, geo, phonons, replicas, start, max_time)
+        print('Total time: %s' % (datetime.now() - start))
+        if out is not None:
+            sys.stdout = sys.__stdout__
+            out.close()
+        return ens
     pop = Population(args, geo, phonons)
     flag = True
     while flag:
@@ -44,14 +75,7 @@ def main(argv=None):
         if max_time.total_seconds() > 0:
             flag = flag and datetime.now() - start < max_time
     print('Saving end of run particle data...')
-    pop.write_final_state(geo)
-    pop.view.postprocess()
-    if pop.n_bands > 0 and pop.rank == 0:
-        pop.write_k_contribution()
-    if pop.field_n is not None and pop.rank == 0:
-        pop.write_field()
-    if pop.modes_every > 0:
-        pop.write_modes()                    # (every rank: the read-out sums over the ranks; rank 0 writes)
+    pop.finish_run(geo)
     total = datetime.now() - start
     print('Total time: %s' % total)
     if out is not None:

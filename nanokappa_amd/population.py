@@ -865,67 +865,83 @@ class Population(Constants):
     def run(self, nsteps, geometry=None, phonon=None):
         """Advance nsteps timesteps.  Library calls are cut at the 100-step bookkeeping boundaries
         (Population.py:1729-1741) so that outputs are identical to stepping one by one."""
+        geometry, phonon = self._begin_run(geometry, phonon)
+        done = 0
+        while done < nsteps:
+            chunk = self._plan_chunk(nsteps - done, geometry)
+            t = self.engine.step(chunk)
+            self._consume_chunk(t, chunk, geometry, phonon)
+            done += chunk
+
+    # run() in its parts, so that an Ensemble (ensemble.py) can step several populations with shared library calls: what comes
+    # before the first chunk of a run, the plan of the next chunk (with the bookkeeping due before it), and what a chunk's tallies
+    # are turned into
+    def _begin_run(self, geometry=None, phonon=None):
         geometry = geometry if geometry is not None else self._geo
         phonon = phonon if phonon is not None else self._ph
         self._geo, self._ph = geometry, phonon
         self._sync_clock()
-        done = 0
-        while done < nsteps:
-            if self.current_timestep == 0:
-                print('Simulating...')
-            if (self.current_timestep % 100) == 0:
-                self._every_hundred(geometry)
-            chunk = min(nsteps - done, 100 - (self.current_timestep % 100))
-            field_on = getattr(self, 'field_n', None) is not None
-            if field_on:                                        # ... and at the ends of the field's averaging windows
-                chunk = min(chunk, self.field_window - (self.current_timestep % self.field_window))
-            modes_on = getattr(self, 'modes_every', 0) > 0
-            if modes_on:                                        # ... and of the mode tally's
-                chunk = min(chunk, self.modes_window - (self.current_timestep % self.modes_window))
-            # the reference grows its arrays as the ensemble grows; here the particle store is re-laid out with head room
-            # before it can fill up (this rank's share of N_p against the engine's slots)
-            # (the engine's slot count only changes when the store grows: asked for again after every 100 steps and after a reserve)
-            local = self.N_p / max(self.nranks, 1)
-            if getattr(self, '_slots', None) is None or (self.current_timestep % 100) == 0:
-                self._slots = self.engine.timing()['slots']
-            if self._slots > 0 and local > 0.8 * self._slots:
-                self.engine.reserve(int(2.0 * local) + 65536)
-                self._slots = None
-            t = self.engine.step(chunk)
-            s0 = 0
-            while s0 < chunk:
-                # up to the next convergence step in one go: only the reservoir tallies accumulate in between
-                to_conv = self.n_dt_to_conv - (self.current_timestep % self.n_dt_to_conv)
-                s1 = min(chunk, s0 + to_conv)
-                s = s1 - 1
-                self.current_timestep += s1 - s0
-                self.t = self.current_timestep * self.dt
-                self.subvol_temperature = t['T_sv'][s]
-                self.subvol_energy = t['E_sv'][s]
-                self.subvol_N_p = t['N_sv'][s].astype(np.int64)
-                self.N_p = int(self.subvol_N_p.sum())
-                self.total_energy = float(t['E_raw'][s].sum())
-                if self.n_of_reservoirs > 0:
-                    self.N_leaving = t['N_leaving'][s].astype(np.int64)
-                    for q in range(s0, s1):                     # same summation order as stepping one by one
-                        self.res_energy_balance = self.res_energy_balance + t['res_energy'][q]
-                        self.res_heat_flux = self.res_heat_flux + t['res_flux'][q]
-                    self._bal_steps += s1 - s0
-                if (self.current_timestep % self.n_dt_to_conv) == 0:                # Population.py:1762-1767
-                    if self.n_bands > 0:                        # this step's band row (nk_step tallied it after the sweep)
-                        r = np.nonzero(t['band_steps'] == self.current_timestep - 1)[0]
-                        self._band_row = (t['band_F'][r[0]], t['band_N'][r[0]]) if r.size else None
-                    self.subvol_heat_flux = self._normalise_flux(phonon, t['flux_raw'][s], self.subvol_N_p)
-                    self.calculate_kappa(geometry)
-                    self.adjust_reservoir_balance(geometry, phonon)
-                    self._record_convergence(geometry)
-                    self.restart_reservoir_balance()
-                s0 = s1
-            done += chunk
-            if field_on and (self.current_timestep % self.field_window) == 0:
-                self._field_window_end()
-            if modes_on and (self.current_timestep % self.modes_window) == 0:
-                self._modes_window_end()
+        return geometry, phonon
+
+    def _plan_chunk(self, left, geometry):
+        """Steps of the next library call (at most `left`), after the bookkeeping that is due before it."""
+        if self.current_timestep == 0:
+            print('Simulating...')
+        if (self.current_timestep % 100) == 0:
+            self._every_hundred(geometry)
+        chunk = min(left, 100 - (self.current_timestep % 100))
+        if getattr(self, 'field_n', None) is not None:      # ... and at the ends of the field's averaging windows
+            chunk = min(chunk, self.field_window - (self.current_timestep % self.field_window))
+        if getattr(self, 'modes_every', 0) > 0:             # ... and of the mode tally's
+            chunk = min(chunk, self.modes_window - (self.current_timestep % self.modes_window))
+        # the reference grows its arrays as the ensemble grows; here the particle store is re-laid out with head room
+        # before it can fill up (this rank's share of N_p against the engine's slots)
+        # (the engine's slot count only changes when the store grows: asked for again after every 100 steps and after a reserve)
+        local = self.N_p / max(self.nranks, 1)
+        if getattr(self, '_slots', None) is None or (self.current_timestep % 100) == 0:
+            self._slots = self.engine.timing()['slots']
+        if self._slots > 0 and local > 0.8 * self._slots:
+            self.engine.reserve(int(2.0 * local) + 65536)
+            self._slots = None
+        return chunk
+
+    def _consume_chunk(self, t, chunk, geometry, phonon):
+        """The tallies `t` of a library call of `chunk` steps: clock, state, reservoir sums, convergence rows."""
+        field_on = getattr(self, 'field_n', None) is not None
+        modes_on = getattr(self, 'modes_every', 0) > 0
+        s0 = 0
+        while s0 < chunk:
+            # up to the next convergence step in one go: only the reservoir tallies accumulate in between
+            to_conv = self.n_dt_to_conv - (self.current_timestep % self.n_dt_to_conv)
+            s1 = min(chunk, s0 + to_conv)
+            s = s1 - 1
+            self.current_timestep += s1 - s0
+            self.t = self.current_timestep * self.dt
+            self.subvol_temperature = t['T_sv'][s]
+            self.subvol_energy = t['E_sv'][s]
+            self.subvol_N_p = t['N_sv'][s].astype(np.int64)
+            self.N_p = int(self.subvol_N_p.sum())
+            self.total_energy = float(t['E_raw'][s].sum())
+            if self.n_of_reservoirs > 0:
+                self.N_leaving = t['N_leaving'][s].astype(np.int64)
+                for q in range(s0, s1):                     # same summation order as stepping one by one
+                    self.res_energy_balance = self.res_energy_balance + t['res_energy'][q]
+                    self.res_heat_flux = self.res_heat_flux + t['res_flux'][q]
+                self._bal_steps += s1 - s0
+            if (self.current_timestep % self.n_dt_to_conv) == 0:                # Population.py:1762-1767
+                if self.n_bands > 0:                        # this step's band row (nk_step tallied it after the sweep)
+                    r = np.nonzero(t['band_steps'] == self.current_timestep - 1)[0]
+                    self._band_row = (t['band_F'][r[0]], t['band_N'][r[0]]) if r.size else None
+                self.subvol_heat_flux = self._normalise_flux(phonon, t['flux_raw'][s], self.subvol_N_p)
+                self.calculate_kappa(geometry)
+                self.adjust_reservoir_balance(geometry, phonon)
+                self._record_convergence(geometry)
+                self.restart_reservoir_balance()
+            s0 = s1
+        if field_on and (self.current_timestep % self.field_window) == 0:
+            self._field_window_end()
+        if modes_on and (self.current_timestep % self.modes_window) == 0:
+            self._modes_window_end()
 
     def _every_hundred(self, geometry):
         if self.results_folder_name and getattr(self.args, 'checkpoint', True):     # every rank: its shard of the particles
@@ -1054,6 +1070,18 @@ class Population(Constants):
         self.f = open(os.path.join(self.results_folder_name, 'convergence.txt'), 'a+')
         self.f.writelines(line + '\n')
         self.f.close()
+
+    def finish_run(self, geometry):
+        """What a driver writes after its time loop (nanokappa.py:100-107 and this build's tallies): the final state, and the
+        conductivity by band, the field maps and the mode tally where they are on."""
+        self.write_final_state(geometry)
+        self.view.postprocess()
+        if self.n_bands > 0 and self.rank == 0:
+            self.write_k_contribution()
+        if self.field_n is not None and self.rank == 0:
+            self.write_field()
+        if self.modes_every > 0:
+            self.write_modes()                   # (every rank: the read-out sums over the ranks; rank 0 writes)
 
     # ------------------------------------------------------------------------------ particle data
     def particles(self):
