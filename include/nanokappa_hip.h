@@ -312,6 +312,39 @@ typedef struct {
 } nk_field_report;
 int nk_field_info(nk_ctx *ctx, nk_field_report *out);
 
+/* Grouped field maps: the field's three sums per (cell, group of modes) -- N, E = sum e_i and F = sum v_i e_i over the
+ * particles of cell c whose mode m has group_of_mode[m] = g.  A group is whatever the caller says (a frequency bin, a branch,
+ * a mean-free-path bin, a direction bin); -1 puts a mode in no group: its particles are added nowhere and counted in
+ * `ungrouped`.  The grid, the cadence (nk_field.every), the bounds, the scales 2^k_E / 2^k_F and the capacity are the
+ * field's, the terms and the cell rule are k_field's, and a sample is taken or dropped together with the field's, so the two
+ * windows always hold the same steps: for a table that groups every mode the sums over g of the integers of a cell are the
+ * field's integers of that cell, bit for bit.  Line of (cell c, group g): c * ngroups + g.  Same bits on the LDS and the
+ * global path (NK_FIELD_GLOBAL and NK_FIELD_PATH=global force the latter here too), from run to run and for any split of
+ * the particles over ranks.
+ * ngroups = 0: off (the default) -- nothing is launched or allocated, everything is freed.  group_of_mode [M], M = Q*J.
+ * NK_ERR_ARG: no field (nk_set_field first), an entry outside [-1, ngroups), more than 2^24 lines (cells x groups);
+ * NK_ERR_HIP (with the byte count) when the allocation fails.  nk_set_field, with a new grid or to switch the field off,
+ * switches the groups off.  While they are on the resident kernel is not used, and a replica group refuses the context (as
+ * for the field). */
+int nk_set_field_groups(nk_ctx *ctx, int32_t ngroups, const int32_t *group_of_mode);
+/* The sums over the field steps since the last reset: N [ncells*G], E [ncells*G], F [ncells*G*3] (any may be NULL), the
+ * number of field steps in them and the particles of ungrouped modes they met; reset != 0 starts a new window (reset the
+ * field's at the same time to keep the two in step).  NK_ERR_CAPACITY, naming the sum, when a term exceeded its bound. */
+int nk_get_field_groups(nk_ctx *ctx, double *N, double *E, double *F, int64_t *samples, int64_t *ungrouped, int32_t reset);
+/* State mode, as nk_tally_field_state: raw [ncells*G*8], per line the integers {N, E 2^k_E, Fx 2^k_F, Fy 2^k_F, Fz 2^k_F, 0,
+ * 0, 0} of this call alone (summed over the ranks of a communicator); clamped counts grouped particles outside the grid. */
+int nk_tally_field_groups_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped, int64_t *ungrouped);
+typedef struct {
+    int32_t G;               /* groups */
+    int32_t lds_path;        /* 1: bins in LDS with one flush per workgroup, 0: global integer adds directly */
+    int64_t lines;           /* ncells * G */
+    int64_t bytes;           /* device memory allocated for the groups (0 when off) */
+    int32_t k_E, k_F;        /* the field's scales */
+    int64_t permutes;        /* times the table was brought into the segments' order (a new table, mode map or store size) */
+    int32_t on, pad_;
+} nk_field_groups_report;
+int nk_field_groups_info(nk_ctx *ctx, nk_field_groups_report *out);
+
 /* Mode-resolved tally: the distribution itself, E[s][m] = sum e_i and N[s][m] over the particles of subvolume s in mode
  * m = q*J + j, at full resolution (S x M bins).  The group velocity is a property of the mode, so the heat flux of a mode is
  * v_m E[s][m] exactly, and any band sum of nk_set_bands is a sum of entries of this table.  One pass over the store per mode

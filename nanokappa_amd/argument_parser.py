@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid` and `--mode_tally`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups` and `--mode_tally`."""
 import argparse
 import os
 import sys
@@ -56,6 +56,11 @@ def initialise_parser(debug_flag=False):
       help='nx ny nz [every]: sum particle count, energy and heat flux on a uniform grid of nx x ny x nz cells over the '
            'bounding box every `every` steps (default 100, a multiple of 10) on the GPU, averaged over the convergence '
            'window, and write field.vtk; the counterpart of the particle scatter of --fig_plot; off by default')
+    a('--field_groups', default=[], type=str, nargs='*',
+      help='G kind [axis]: with --field_grid, also sum count, energy and heat flux per (cell, group of modes) on the GPU and '
+           'write field_groups.npz; kind = frequency (G bins), branch (one group per branch), mfp (G log-spaced bins of the '
+           'mean free path at the mean reservoir temperature) or direction (G bins of the cosine between the group velocity '
+           'and the axis x|y|z, default the slice axis); off by default')
     a('--mode_tally', default=['0'], type=str, nargs='*',
       help='[every]: tally energy and particle count per (subvolume, mode) every `every` steps (default 100, a multiple of '
            'n_dt_to_conv = 10) on the GPU over the convergence window, and write mode_tally.npz and the conductivity '

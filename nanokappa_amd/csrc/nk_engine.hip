@@ -20,6 +20,7 @@
 #include "../../include/nanokappa_hip.h"
 #include "nk_kernels.h"
 #include "nk_field.h"
+#include "nk_fgroups.h"
 #include "nk_modes.h"
 #include "nk_group.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
@@ -140,6 +141,9 @@ struct nk_ctx {
     std::vector<int64_t> band_steps;     //   and the absolute step of each
     // spatial field maps (nk_set_field, k_field; nk_field.hip): off by default -- then nothing is launched or allocated
     NkFieldHost field;
+    // grouped field maps (nk_set_field_groups, k_field_groups; nk_fgroups.hip): off by default, need a field
+    NkFGroupsHost fgroups;
+    int64_t map_gen = 0;                 // counts nk_build_mode_map: the groups' permuted table follows the mode map
     // mode-resolved tally (nk_set_modes, k_modes; nk_modes.hip): off by default -- then nothing is launched or allocated
     NkModesHost modes;
     double res_T_max = 0.0;              // highest reservoir temperature (nk_set_reservoirs): bounds the field's terms
@@ -453,6 +457,7 @@ void nk_destroy(nk_ctx *ctx) {
     if (ctx->band_slabs) hipFree(ctx->band_slabs);
     if (ctx->band_rows_d) hipFree(ctx->band_rows_d);
     nk_field_free(ctx->field);
+    nk_fgroups_free(ctx->fgroups);
     nk_modes_free(ctx->modes);
     hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1349,6 +1354,7 @@ static int nk_build_mode_map(nk_ctx *ctx) {
     if (ctx->nl_dev) { hipFree(ctx->nl_dev); ctx->nl_dev = nullptr; }
     d.m2s = nullptr; d.s2m = nullptr; d.seg_nl = nullptr;
     ctx->h_m2s.clear(); ctx->h_s2m.clear(); ctx->map_nseg = 0;
+    ctx->map_gen += 1;
     if (d.M <= 0 || d.nseg <= 0) return NK_OK;
     const int M = d.M, nseg = d.nseg, nlmax = d.nlmax;
     const bool plain = !d.part;          // developer probe without the partition: the modes' emission is dealt m % nseg, forwards
@@ -1960,6 +1966,46 @@ static int nk_field_status(nk_ctx *ctx, long long st[4], const char *who) {
     return NK_OK;
 }
 
+// ---- grouped field maps (k_field_groups; nk_fgroups.hip).  Grid, cadence, bounds and scales are the field's, so the field's
+// refresh serves both; what is the groups' own is the table in the segments' order, rebuilt wherever the field looks at its
+// scales again (a new mode map, a store that has grown).
+static int nk_fgroups_refresh(nk_ctx *ctx) {
+    const hipError_t e = nk_fgroups_permute(ctx->fgroups, ctx->d, ctx->map_gen, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->err = "nk_set_field_groups: the table in the segments' order (" + std::to_string((long long)ctx->d.nseg * ctx->d.nlmax * 4) +
+                   " bytes): " + hipGetErrorString(e);
+        return NK_ERR_HIP;
+    }
+    return NK_OK;
+}
+static int nk_fgroups_sample(nk_ctx *ctx, bool state) {
+    NkFGroupsHost &Gh = ctx->fgroups;
+    NK_HIP(nk_fgroups_pass(Gh, ctx->field, ctx->d, state, nk_lds(ctx, false), ctx->num_cu, ctx->stream));
+    if (ctx->comm) {
+        ncclResult_t nrc = ctx->rccl.AllReduce(Gh.grid, Gh.grid, ((size_t)Gh.lines + 1) * 8, ncclInt64, ncclSum, ctx->comm, ctx->stream);
+        if (nrc != ncclSuccess) { ctx->err = "ncclAllReduce of the field groups' grid failed"; return NK_ERR_COMM; }
+    }
+    return NK_OK;
+}
+static std::string nk_fgroups_overflow(const nk_ctx *ctx, const char *who, long long ovE, long long ovF) {
+    return std::string(who) + ": field groups overflow: " + std::to_string(ovE) + " term(s) of E above B_E = " + std::to_string(ctx->field.BE) +
+           " eV, " + std::to_string(ovF) + " term(s) of F above B_F = " + std::to_string(ctx->field.BF) +
+           " (occupations outside the material's temperature range?); they were left out of the sums";
+}
+// The status words {samples, clamped, overflow E, overflow F, ungrouped}; a term above its bound is an error that names the sum.
+static int nk_fgroups_status(nk_ctx *ctx, long long st[8], const char *who) {
+    NkFGroupsHost &Gh = ctx->fgroups;
+    NK_HIP(hipMemcpy(st, Gh.status, 8 * sizeof(long long), hipMemcpyDeviceToHost));
+    if (st[NK_FG_ST_OVE] || st[NK_FG_ST_OVF]) {
+        long long z[2] = {0, 0};
+        NK_HIP(hipMemcpy(Gh.status + NK_FG_ST_OVE, z, sizeof(z), hipMemcpyHostToDevice));
+        ctx->err = nk_fgroups_overflow(ctx, who, st[NK_FG_ST_OVE], st[NK_FG_ST_OVF]);
+        return NK_ERR_CAPACITY;
+    }
+    return NK_OK;
+}
+
 // ---- mode-resolved tally (k_modes; nk_modes.hip).  Bound and scale as the field's, looked at again at the same places.
 static double nk_modes_T_hi(const nk_ctx *ctx) {
     const NkDev &d = ctx->d;
@@ -2192,6 +2238,12 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
             int rcf_ = nk_field_sample(ctx, false);
             if (rcf_) return rcf_;
             NK_HIP(nk_field_accumulate(ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
+            // ... and the same sums per (cell, group of modes): taken or dropped with the field's sample
+            if (ctx->fgroups.on) {
+                int rcg_ = nk_fgroups_sample(ctx, false);
+                if (rcg_) return rcg_;
+                NK_HIP(nk_fgroups_accumulate(ctx->fgroups, ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
+            }
         }
         // the mode-resolved tally of the same particles on mode steps (k_modes: one wave per segment)
         if (ctx->modes.on && do_flux && ((stepno + 1) % ctx->modes.cfg.every) == 0) {
@@ -2494,6 +2546,7 @@ static int nk_step_begin(nk_ctx *ctx) {
     ctx->band_rows.clear();
     ctx->band_steps.clear();
     if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;
+    if (ctx->fgroups.on && (rc = nk_fgroups_refresh(ctx))) return rc;
     if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;
     return NK_OK;
 }
@@ -2572,6 +2625,7 @@ static int nk_step_consume(nk_ctx *ctx, int32_t nsteps, nk_tally *out, NkStepRun
         }
         if ((rc = nk_update_tau_window(ctx, false))) return rc;
         if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;     // the store has grown: the field's scales follow
+        if (ctx->fgroups.on && (rc = nk_fgroups_refresh(ctx))) return rc; // ... and the groups' table in the segments' order
         if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;     // ... and the mode tally's
     }
     return NK_OK;
@@ -2598,7 +2652,16 @@ static int nk_step_end(nk_ctx *ctx, int overflow) {
     }
     if (ctx->field.on) {
         long long st[4];
-        if ((rc = nk_field_status(ctx, st, "nk_step"))) return rc;
+        rc = nk_field_status(ctx, st, "nk_step");
+        if (ctx->fgroups.on) {                           // (both are read, so that neither keeps a stale overflow for the next call)
+            const std::string ef = ctx->err;
+            long long sg[8];
+            const int rcg = nk_fgroups_status(ctx, sg, "nk_step");
+            if (rc && rcg == NK_ERR_CAPACITY) ctx->err = ef + "; " + ctx->err;
+            else if (rc) ctx->err = ef;
+            if (!rc) rc = rcg;
+        }
+        if (rc) return rc;
     }
     if (ctx->modes.on) {
         long long st[4];
@@ -3321,6 +3384,7 @@ int nk_set_field(nk_ctx *ctx, const nk_field *f) {
     NK_HIP(hipSetDevice(ctx->device));
     NK_HIP(hipStreamSynchronize(ctx->stream));
     nk_field_free(ctx->field);
+    nk_fgroups_free(ctx->fgroups);
     if (f->n[0] == 0 && f->n[1] == 0 && f->n[2] == 0) return NK_OK;
     NK_ARG(ctx->have_material && ctx->have_sv, "nk_set_field: set the material and the subvolumes first");
     const NkDev &d = ctx->d;
@@ -3406,6 +3470,93 @@ int nk_field_info(nk_ctx *ctx, nk_field_report *out) {
     out->capacity = fh.capacity;
     out->bytes = fh.bytes;
     out->lds_path = nk_field_lds_bins(fh, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_field_pass asks, too)
+    out->on = 1;
+    return NK_OK;
+}
+
+// ---- grouped field maps: the field's sums per (cell, group of modes)
+int nk_set_field_groups(nk_ctx *ctx, int32_t ngroups, const int32_t *group_of_mode) {
+    NK_ARG(ctx, "nk_set_field_groups: bad arguments");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    nk_fgroups_free(ctx->fgroups);
+    if (ngroups == 0) return NK_OK;
+    NK_ARG(ngroups > 0 && group_of_mode, "nk_set_field_groups: ngroups must not be negative and the table is required");
+    int rc = nk_fgroups_configure(ctx->fgroups, ctx->field, ngroups, group_of_mode, ctx->d.M, ctx->err);
+    if (rc) return rc;
+    if (ctx->d.cap > 0 && (rc = nk_fgroups_refresh(ctx))) return rc;
+    return NK_OK;
+}
+
+int nk_get_field_groups(nk_ctx *ctx, double *N, double *E, double *F, int64_t *samples, int64_t *ungrouped, int32_t reset) {
+    NK_ARG(ctx, "nk_get_field_groups: bad arguments");
+    NkFGroupsHost &Gh = ctx->fgroups;
+    NK_ARG(Gh.on, "nk_get_field_groups: no groups were set (nk_set_field_groups)");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t nl = (size_t)Gh.lines;
+    std::vector<double> a(nl * 5);
+    NK_HIP(hipMemcpy(a.data(), Gh.acc, a.size() * sizeof(double), hipMemcpyDeviceToHost));
+    long long st[8];
+    int rc = nk_fgroups_status(ctx, st, "nk_get_field_groups");
+    if (rc) return rc;
+    for (size_t b = 0; b < nl; ++b) {
+        if (N) N[b] = a[5 * b];
+        if (E) E[b] = a[5 * b + 1];
+        if (F) { F[3 * b] = a[5 * b + 2]; F[3 * b + 1] = a[5 * b + 3]; F[3 * b + 2] = a[5 * b + 4]; }
+    }
+    if (samples) *samples = st[NK_FG_ST_SAMPLES];
+    if (ungrouped) *ungrouped = st[NK_FG_ST_UNGROUPED];
+    if (reset) {
+        NK_HIP(hipMemset(Gh.acc, 0, a.size() * sizeof(double)));
+        NK_HIP(hipMemset(Gh.status, 0, 8 * sizeof(long long)));
+    }
+    return NK_OK;
+}
+
+int nk_tally_field_groups_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped, int64_t *ungrouped) {
+    NK_ARG(ctx && raw, "nk_tally_field_groups_state: bad arguments");
+    NkFGroupsHost &Gh = ctx->fgroups;
+    NK_ARG(Gh.on, "nk_tally_field_groups_state: no groups were set (nk_set_field_groups)");
+    int rc = nk_check_ready(ctx);
+    if (rc) return rc;
+    NK_HIP(hipSetDevice(ctx->device));
+    NkDev &d = ctx->d;
+    if ((rc = nk_normalize(ctx))) return rc;
+    if (ctx->pending_relax) {                          // the state the caller means includes the deferred relaxation
+        k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 0);
+        ctx->pending_relax = false;
+    }
+    if ((rc = nk_field_refresh(ctx))) return rc;
+    if ((rc = nk_fgroups_refresh(ctx))) return rc;
+    if ((rc = nk_fgroups_sample(ctx, true))) return rc;
+    const size_t nl = (size_t)Gh.lines;
+    std::vector<int64_t> h((nl + 1) * 8);
+    NK_HIP(hipMemcpyAsync(h.data(), Gh.grid, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(nk_fgroups_clear_grid(Gh, ctx->stream));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    const int64_t *hdr = h.data() + nl * 8;
+    if (hdr[NK_FG_OVE] || hdr[NK_FG_OVF]) {
+        ctx->err = nk_fgroups_overflow(ctx, "nk_tally_field_groups_state", (long long)hdr[NK_FG_OVE], (long long)hdr[NK_FG_OVF]);
+        return NK_ERR_CAPACITY;
+    }
+    memcpy(raw, h.data(), nl * 8 * sizeof(int64_t));
+    if (clamped) *clamped = hdr[NK_FG_CLAMPED];
+    if (ungrouped) *ungrouped = hdr[NK_FG_UNGROUPED];
+    return NK_OK;
+}
+
+int nk_field_groups_info(nk_ctx *ctx, nk_field_groups_report *out) {
+    NK_ARG(ctx && out, "nk_field_groups_info: NULL argument");
+    memset(out, 0, sizeof(*out));
+    const NkFGroupsHost &Gh = ctx->fgroups;
+    if (!Gh.on) return NK_OK;
+    out->G = Gh.G;
+    out->lines = Gh.lines;
+    out->bytes = Gh.bytes;
+    out->lds_path = nk_fgroups_lds_bins(Gh, ctx->field, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_fgroups_pass asks, too)
+    out->k_E = ctx->field.kE; out->k_F = ctx->field.kF;
+    out->permutes = Gh.permutes;
     out->on = 1;
     return NK_OK;
 }

@@ -89,6 +89,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
            'nk_tally_bands_state', 'nk_set_field', 'nk_get_field', 'nk_tally_field_state', 'nk_field_info',
+           'nk_set_field_groups', 'nk_get_field_groups', 'nk_tally_field_groups_state', 'nk_field_groups_info',
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error']
 
@@ -101,6 +102,11 @@ class nk_field_report(C.Structure):
     _fields_ = [('n', C.c_int32 * 3), ('every', C.c_int32), ('ncells', C.c_int64), ('k_E', C.c_int32), ('k_F', C.c_int32),
                 ('B_E', C.c_double), ('B_F', C.c_double), ('capacity', C.c_int64), ('bytes', C.c_int64),
                 ('lds_path', C.c_int32), ('on', C.c_int32)]
+
+
+class nk_field_groups_report(C.Structure):
+    _fields_ = [('G', C.c_int32), ('lds_path', C.c_int32), ('lines', C.c_int64), ('bytes', C.c_int64), ('k_E', C.c_int32),
+                ('k_F', C.c_int32), ('permutes', C.c_int64), ('on', C.c_int32), ('pad_', C.c_int32)]
 
 
 class nk_modes(C.Structure):
@@ -189,6 +195,10 @@ def load_library():
     L.nk_get_field.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
     L.nk_tally_field_state.argtypes = [C.c_void_p, c_i64p, c_i64p]
     L.nk_field_info.argtypes = [C.c_void_p, C.POINTER(nk_field_report)]
+    L.nk_set_field_groups.argtypes = [C.c_void_p, C.c_int32, c_ip]
+    L.nk_get_field_groups.argtypes = [C.c_void_p, c_dp, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
+    L.nk_tally_field_groups_state.argtypes = [C.c_void_p, c_i64p, c_i64p, c_i64p]
+    L.nk_field_groups_info.argtypes = [C.c_void_p, C.POINTER(nk_field_groups_report)]
     L.nk_set_modes.argtypes = [C.c_void_p, C.POINTER(nk_modes)]
     L.nk_get_modes.argtypes = [C.c_void_p, c_dp, c_dp, c_i64p, c_i64p, C.c_int32]
     L.nk_tally_modes_state.argtypes = [C.c_void_p, c_i64p, c_i64p]
@@ -501,6 +511,7 @@ class Engine(object):
             f.n[a] = n[a]
         f.every, f.flags, f.capacity = int(every), int(flags), int(capacity)
         self._field_n = None
+        self._fgroups_G = 0                                 # (nk_set_field switches the groups off)
         self._ck(self.L.nk_set_field(self.h, C.byref(f)), 'nk_set_field')
         self._field_n = tuple(n) if any(n) else None
 
@@ -535,6 +546,57 @@ class Engine(object):
         info = self.field_info()
         kE, kF = info['k_E'], info['k_F']
         return dict(raw=raw, k_E=kE, k_F=kF, clamped=int(cl.value), N=raw[..., 0].astype(np.float64),
+                    E=np.ldexp(raw[..., 1].astype(np.float64), -kE), F=np.ldexp(raw[..., 2:5].astype(np.float64), -kF))
+
+    # ------------------------------------------------------- grouped field maps
+    def set_field_groups(self, group_of_mode, ngroups):
+        """The field's sums per (cell, group of modes) (nk_set_field_groups; k_field_groups): group_of_mode [M] gives every
+        mode its group in [0, ngroups) or -1 for none.  Needs a field (set_field): grid, cadence and scales are the field's.
+        ngroups = 0 turns it off and frees its tables."""
+        ngroups = int(ngroups)
+        self._fgroups_G = 0
+        if ngroups == 0:
+            self._ck(self.L.nk_set_field_groups(self.h, 0, None), 'nk_set_field_groups')
+            return
+        g = _i(np.ravel(group_of_mode))
+        if g.shape[0] != self.M:
+            raise NkError('set_field_groups: group_of_mode needs one entry per mode (%d), got %d' % (self.M, g.shape[0]))
+        self._ck(self.L.nk_set_field_groups(self.h, ngroups, _p(g, c_ip)), 'nk_set_field_groups')
+        self._fgroups_G = ngroups
+
+    def field_groups_info(self):
+        """nk_field_groups_info: groups, lines (cells x groups), bytes allocated, path in use, the field's scales, and how often
+        the table was brought into the segments' order."""
+        r = nk_field_groups_report()
+        self._ck(self.L.nk_field_groups_info(self.h, C.byref(r)), 'nk_field_groups_info')
+        return dict(G=int(r.G), lines=int(r.lines), bytes=int(r.bytes), lds_path=int(r.lds_path), k_E=int(r.k_E), k_F=int(r.k_F),
+                    permutes=int(r.permutes), on=int(r.on))
+
+    def _fgroups_shape(self, who):
+        if not getattr(self, '_fgroups_G', 0) or getattr(self, '_field_n', None) is None:
+            raise NkError('%s: no groups were set (set_field_groups)' % who)
+        return self._field_n + (self._fgroups_G,)
+
+    def field_groups(self, reset=False):
+        """The sums over the field steps since the last reset (all ranks): dict N, E (nx, ny, nz, G), F (nx, ny, nz, G, 3),
+        samples (field steps in the sums) and ungrouped (particles of modes in no group)."""
+        n = self._fgroups_shape('field_groups')
+        N, E, F = np.zeros(n), np.zeros(n), np.zeros(n + (3,))
+        sm, ug = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.nk_get_field_groups(self.h, _p(N), _p(E), _p(F), C.byref(sm), C.byref(ug), 1 if reset else 0), 'nk_get_field_groups')
+        return dict(N=N, E=E, F=F, samples=int(sm.value), ungrouped=int(ug.value))
+
+    def tally_field_groups_state(self):
+        """State mode (nk_tally_field_groups_state), as tally_field_state: dict raw (nx, ny, nz, G, 8) int64 = {N, E 2^k_E,
+        F 2^k_F (3), 0, 0, 0}, k_E, k_F, clamped, ungrouped, and the reals N, E, F they stand for."""
+        n = self._fgroups_shape('tally_field_groups_state')
+        raw = np.zeros(n + (8,), dtype=np.int64)
+        cl, ug = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.nk_tally_field_groups_state(self.h, raw.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cl), C.byref(ug)),
+                 'nk_tally_field_groups_state')
+        info = self.field_groups_info()
+        kE, kF = info['k_E'], info['k_F']
+        return dict(raw=raw, k_E=kE, k_F=kF, clamped=int(cl.value), ungrouped=int(ug.value), N=raw[..., 0].astype(np.float64),
                     E=np.ldexp(raw[..., 1].astype(np.float64), -kE), F=np.ldexp(raw[..., 2:5].astype(np.float64), -kF))
 
     # ------------------------------------------------------- mode-resolved tally

@@ -22,6 +22,7 @@ from .constants import Constants
 from . import setup_tables as ST
 from . import spectral as SP
 from . import field as FD
+from . import field_groups as FG
 from . import modes as MD
 from .engine import Engine
 from .sharding import shard_range
@@ -197,6 +198,11 @@ class Population(Constants):
             self.set_field(fn, fev, geometry)
         elif getattr(args, 'fig_plot', None) and self.rank == 0:
             print('--fig_plot is not drawn by this build; --field_grid nx ny nz [every] writes the same quantities on a grid (field.vtk)')
+        # the same sums per (cell, group of modes) (--field_groups G kind [axis]; needs --field_grid)
+        gG, gkind, gaxis = FG.field_groups_option(getattr(args, 'field_groups', None))
+        FG.require_field(gG, self.field_n)
+        if gG > 0:
+            self.set_field_groups(gkind, gG, gaxis, phonon)
         # mode-resolved tally (--mode_tally [every]; off by default): E and N per (subvolume, mode) on the device
         self.modes_every = 0
         mev = MD.mode_tally_option(getattr(args, 'mode_tally', None), self.n_dt_to_conv)
@@ -289,6 +295,7 @@ class Population(Constants):
         n_dt_to_conv) from here on (Engine.set_field); n = None: off."""
         geometry = geometry if geometry is not None else self._geo
         self._field_last = None
+        self.fgroups_G, self._fgroups_last = 0, None            # (a new field switches the groups off: Engine.set_field)
         if n is None:
             self.engine.set_field((0, 0, 0), (1, 1, 1), (0, 0, 0), 1)
             self.field_n = None
@@ -310,6 +317,11 @@ class Population(Constants):
         last = self.engine.field(reset=True)
         if last['samples'] > 0:
             self._field_last = last
+        if getattr(self, 'fgroups_G', 0) > 0:                   # the groups' window holds the same steps: read and restarted together
+            lg = self.engine.field_groups(reset=True)
+            if lg['samples'] > 0:
+                lg.update(N_cell=last['N'], step=int(self.current_timestep))
+                self._fgroups_last = lg
 
     def field(self):
         """The field, normalised the reference's way per cell (field.normalise): dict N (mean particles per cell and field
@@ -344,6 +356,71 @@ class Population(Constants):
         return FD.write_vtk(FD.field_path(self.results_folder_name), f['lo'], f['h'], f['n'], f['N'], f['T'], f['energy'],
                             f['heat_flux'], title='nanokappa field: mean over %d field steps up to timestep %d'
                             % (f['samples'], self.current_timestep))
+
+    # ----------------------------------------------------------------------- grouped field maps
+    def set_field_groups(self, kind, G, axis=None, phonon=None):
+        """Sum N, E, F per (cell of the field's grid, group of modes) on the field's steps from here on (Engine.set_field_groups).
+        kind: frequency (G bins), branch, mfp (G log-spaced bins of the mean free path at the mean reservoir temperature, without
+        reservoirs the reference temperature, or the mean subvolume temperature where that is 'local'), direction (G bins of the cosine between the group velocity and `axis`,
+        default the slice axis), or an array with the group of every mode; G = 0 or kind = None: off.  Needs a field."""
+        phonon = phonon if phonon is not None else self._ph
+        self._fgroups_last = None
+        if not G or kind is None:
+            self.engine.set_field_groups(None, 0)
+            self.fgroups_G = 0
+            return
+        if self.field_n is None:
+            raise ValueError('--field_groups requires --field_grid nx ny nz [every]: the groups are summed on the field\'s grid')
+        if isinstance(kind, str):
+            if axis is None:
+                axis = int(getattr(self, 'slice_axis', 0) or 0)
+            T = None
+            if kind == 'mfp':
+                rt = np.asarray(getattr(self, 'res_facet_temperature', np.zeros(0)), dtype=float)
+                rt = rt[np.isfinite(rt)]
+                if rt.size:
+                    T = float(rt.mean())
+                elif self.T_reference == 'local':       # no reservoirs and no fixed reference: the subvolumes' own mean
+                    T = float(np.mean(self.subvol_temperature))
+                else:
+                    T = float(self.T_reference)
+            table, G, edges = FG.build_groups(kind, int(G), phonon, T=T, axis=axis)
+            self.fgroups_kind = kind
+        else:
+            table, G, edges = SP.band_map(phonon.omega, int(G), kind)
+            self.fgroups_kind = 'table'
+        self.engine.set_field_groups(table, G)
+        self.engine.field(reset=True)                           # both windows start here, so that they hold the same steps
+        self._field_last = None
+        self.fgroups_G, self.fgroups_table, self.fgroups_edges = int(G), table, edges
+
+    def field_groups(self):
+        """The grouped field: dict N, E (nx, ny, nz, G), F (.., 3) (sums over `samples` field steps), heat_flux (W/m^2, normalised
+        per cell with the field's total count: the groups' heat fluxes add up to the field's), energy (the groups' shares of
+        the deviational energy density), samples, ungrouped, step, kind, edges, lo, h, n.  The latest COMPLETE field window
+        and, until the first one is complete, the field steps so far -- the same steps as Population.field()."""
+        if getattr(self, 'fgroups_G', 0) <= 0:
+            raise RuntimeError('field_groups: no groups (--field_groups or Population.set_field_groups)')
+        raw = self._fgroups_last
+        if raw is None:
+            raw = self.engine.field_groups()
+            raw.update(N_cell=self.engine.field()['N'], step=int(self.current_timestep))
+        ph = self._ph
+        nm = FG.normalise(raw['N'], raw['E'], raw['F'], raw['N_cell'], raw['samples'], ph.number_of_active_modes,
+                          ph.number_of_qpoints * ph.volume_unitcell, self.eVpsa2_in_Wm2, norm=self.norm,
+                          particle_density=self.particle_density, cell_volume=float(np.prod(self.field_h)))
+        return dict(N=raw['N'], E=raw['E'], F=raw['F'], heat_flux=nm['heat_flux'], energy=nm['energy'], samples=raw['samples'],
+                    ungrouped=raw['ungrouped'], step=raw['step'], kind=self.fgroups_kind, edges=self.fgroups_edges,
+                    lo=self.field_lo, h=self.field_h, n=self.field_n)
+
+    def write_field_groups(self):
+        if getattr(self, 'fgroups_G', 0) <= 0 or not self.results_folder_name:
+            return None
+        g = self.field_groups()
+        if g['samples'] == 0:
+            return None
+        return FG.write_field_groups(FG.field_groups_path(self.results_folder_name), g['lo'], g['h'], g['n'], g['kind'], g['edges'],
+                                     g['N'], g['E'], g['F'], g['heat_flux'], g['samples'], g['step'])
 
     # ----------------------------------------------------------------------- mode-resolved tally
     def set_modes(self, every=FD.FIELD_EVERY_DEFAULT):
@@ -854,6 +931,8 @@ class Population(Constants):
             self.restart_reservoir_balance()
             if getattr(self, 'field_n', None) is not None:      # the field's window in progress no longer lines up: start again
                 self.engine.field(reset=True)
+                if getattr(self, 'fgroups_G', 0) > 0:
+                    self.engine.field_groups(reset=True)
             if getattr(self, 'modes_every', 0) > 0:             # ... and the mode tally's
                 self.engine.modes(reset=True)
 
@@ -951,6 +1030,7 @@ class Population(Constants):
             self.write_k_contribution()
         if getattr(self, 'field_n', None) is not None and self.rank == 0:     # (the accumulator is the same on every rank)
             self.write_field()
+            self.write_field_groups()
         if getattr(self, 'modes_every', 0) > 0:
             self.write_modes()
         self.update_residue(geometry)
@@ -1080,6 +1160,7 @@ class Population(Constants):
             self.write_k_contribution()
         if self.field_n is not None and self.rank == 0:
             self.write_field()
+            self.write_field_groups()
         if self.modes_every > 0:
             self.write_modes()                   # (every rank: the read-out sums over the ranks; rank 0 writes)
 
