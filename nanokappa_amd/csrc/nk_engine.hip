@@ -20,7 +20,6 @@
 #include "../../include/nanokappa_hip.h"
 #include "nk_kernels.h"
 #include "nk_field.h"
-#include "nk_fgroups.h"
 #include "nk_modes.h"
 #include "nk_group.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
@@ -141,7 +140,7 @@ struct nk_ctx {
     std::vector<int64_t> band_steps;     //   and the absolute step of each
     // spatial field maps (nk_set_field, k_field; nk_field.hip): off by default -- then nothing is launched or allocated
     NkFieldHost field;
-    // grouped field maps (nk_set_field_groups, k_field_groups; nk_fgroups.hip): off by default, need a field
+    // grouped field maps (nk_set_field_groups, k_field<., true>; nk_field.hip): off by default, need a field
     NkFGroupsHost fgroups;
     int64_t map_gen = 0;                 // counts nk_build_mode_map: the groups' permuted table follows the mode map
     // mode-resolved tally (nk_set_modes, k_modes; nk_modes.hip): off by default -- then nothing is launched or allocated
@@ -1941,32 +1940,7 @@ static int nk_field_refresh(nk_ctx *ctx) {
     if (slots != F.capacity) nk_field_scale(F, slots);
     return NK_OK;
 }
-// One pass into the integer grid; summed over the ranks (integers: the result does not depend on who held which particle).
-static int nk_field_sample(nk_ctx *ctx, bool state) {
-    NkFieldHost &F = ctx->field;
-    NK_HIP(nk_field_pass(F, ctx->d, state, nk_lds(ctx, false), ctx->num_cu, ctx->stream));
-    if (ctx->comm) {
-        ncclResult_t nrc = ctx->rccl.AllReduce(F.grid, F.grid, ((size_t)F.ncells + 1) * 8, ncclInt64, ncclSum, ctx->comm, ctx->stream);
-        if (nrc != ncclSuccess) { ctx->err = "ncclAllReduce of the field grid failed"; return NK_ERR_COMM; }
-    }
-    return NK_OK;
-}
-// The status words {samples, clamped, overflow E, overflow F}; a term above its bound is an error that names the sum.
-static int nk_field_status(nk_ctx *ctx, long long st[4], const char *who) {
-    NkFieldHost &F = ctx->field;
-    NK_HIP(hipMemcpy(st, F.status, 4 * sizeof(long long), hipMemcpyDeviceToHost));
-    if (st[2] || st[3]) {
-        long long z[2] = {0, 0};
-        NK_HIP(hipMemcpy(F.status + 2, z, sizeof(z), hipMemcpyHostToDevice));
-        ctx->err = std::string(who) + ": field overflow: " + std::to_string(st[2]) + " term(s) of E above B_E = " + std::to_string(F.BE) +
-                   " eV, " + std::to_string(st[3]) + " term(s) of F above B_F = " + std::to_string(F.BF) +
-                   " (occupations outside the material's temperature range?); they were left out of the sums";
-        return NK_ERR_CAPACITY;
-    }
-    return NK_OK;
-}
-
-// ---- grouped field maps (k_field_groups; nk_fgroups.hip).  Grid, cadence, bounds and scales are the field's, so the field's
+// ---- grouped field maps (k_field<., true>; nk_field.hip).  Grid, cadence, bounds and scales are the field's, so the field's
 // refresh serves both; what is the groups' own is the table in the segments' order, rebuilt wherever the field looks at its
 // scales again (a new mode map, a store that has grown).
 static int nk_fgroups_refresh(nk_ctx *ctx) {
@@ -1979,29 +1953,57 @@ static int nk_fgroups_refresh(nk_ctx *ctx) {
     }
     return NK_OK;
 }
-static int nk_fgroups_sample(nk_ctx *ctx, bool state) {
-    NkFGroupsHost &Gh = ctx->fgroups;
-    NK_HIP(nk_fgroups_pass(Gh, ctx->field, ctx->d, state, nk_lds(ctx, false), ctx->num_cu, ctx->stream));
+// ---- what the field's grid and the groups' share (grouped: which of the two)
+static NkFieldGrid &nk_field_grid(nk_ctx *ctx, bool grouped) { return grouped ? ctx->fgroups.g : ctx->field.g; }
+// One pass into the integer grid; summed over the ranks (integers: the result does not depend on who held which particle).
+static int nk_field_sample(nk_ctx *ctx, bool grouped, bool state) {
+    NkFieldGrid &g = nk_field_grid(ctx, grouped);
+    NK_HIP(nk_field_pass(ctx->field, grouped ? &ctx->fgroups : nullptr, ctx->d, state, nk_lds(ctx, false), ctx->num_cu, ctx->stream));
     if (ctx->comm) {
-        ncclResult_t nrc = ctx->rccl.AllReduce(Gh.grid, Gh.grid, ((size_t)Gh.lines + 1) * 8, ncclInt64, ncclSum, ctx->comm, ctx->stream);
-        if (nrc != ncclSuccess) { ctx->err = "ncclAllReduce of the field groups' grid failed"; return NK_ERR_COMM; }
+        ncclResult_t nrc = ctx->rccl.AllReduce(g.grid, g.grid, ((size_t)g.lines + 1) * 8, ncclInt64, ncclSum, ctx->comm, ctx->stream);
+        if (nrc != ncclSuccess) { ctx->err = std::string("ncclAllReduce of the ") + (grouped ? "field groups'" : "field") + " grid failed"; return NK_ERR_COMM; }
     }
     return NK_OK;
 }
-static std::string nk_fgroups_overflow(const nk_ctx *ctx, const char *who, long long ovE, long long ovF) {
-    return std::string(who) + ": field groups overflow: " + std::to_string(ovE) + " term(s) of E above B_E = " + std::to_string(ctx->field.BE) +
-           " eV, " + std::to_string(ovF) + " term(s) of F above B_F = " + std::to_string(ctx->field.BF) +
-           " (occupations outside the material's temperature range?); they were left out of the sums";
+static const char NK_FIELD_LEFT_OUT[] = " (occupations outside the material's temperature range?); they were left out of the sums";
+static std::string nk_field_overflow(const nk_ctx *ctx, bool grouped, const char *who, long long ovE, long long ovF) {
+    return std::string(who) + (grouped ? ": field groups overflow: " : ": field overflow: ") + std::to_string(ovE) + " term(s) of E above B_E = " +
+           std::to_string(ctx->field.BE) + " eV, " + std::to_string(ovF) + " term(s) of F above B_F = " + std::to_string(ctx->field.BF);
 }
-// The status words {samples, clamped, overflow E, overflow F, ungrouped}; a term above its bound is an error that names the sum.
-static int nk_fgroups_status(nk_ctx *ctx, long long st[8], const char *who) {
-    NkFGroupsHost &Gh = ctx->fgroups;
-    NK_HIP(hipMemcpy(st, Gh.status, 8 * sizeof(long long), hipMemcpyDeviceToHost));
-    if (st[NK_FG_ST_OVE] || st[NK_FG_ST_OVF]) {
+// The status words {samples, clamped, overflow E, overflow F [, ungrouped]} (the field's 4, the groups' 8); a term above its
+// bound is an error that names the sum.
+static int nk_field_status(nk_ctx *ctx, bool grouped, long long st[8], const char *who) {
+    NkFieldGrid &g = nk_field_grid(ctx, grouped);
+    NK_HIP(hipMemcpy(st, g.status, (size_t)g.nstatus * sizeof(long long), hipMemcpyDeviceToHost));
+    if (st[NK_FIELD_ST_OVE] || st[NK_FIELD_ST_OVF]) {
         long long z[2] = {0, 0};
-        NK_HIP(hipMemcpy(Gh.status + NK_FG_ST_OVE, z, sizeof(z), hipMemcpyHostToDevice));
-        ctx->err = nk_fgroups_overflow(ctx, who, st[NK_FG_ST_OVE], st[NK_FG_ST_OVF]);
+        NK_HIP(hipMemcpy(g.status + NK_FIELD_ST_OVE, z, sizeof(z), hipMemcpyHostToDevice));
+        ctx->err = nk_field_overflow(ctx, grouped, who, st[NK_FIELD_ST_OVE], st[NK_FIELD_ST_OVF]) + NK_FIELD_LEFT_OUT;
         return NK_ERR_CAPACITY;
+    }
+    return NK_OK;
+}
+// The accumulator of a grid as N [lines], E [lines], F [lines][3] and two of its status words; reset = start a new window.
+static int nk_field_get(nk_ctx *ctx, bool grouped, const char *who, double *N, double *E, double *F, int64_t *samples, int64_t *count, int count_word, int32_t reset) {
+    NkFieldGrid &g = nk_field_grid(ctx, grouped);
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t nl = (size_t)g.lines;
+    std::vector<double> a(nl * 5);
+    NK_HIP(hipMemcpy(a.data(), g.acc, a.size() * sizeof(double), hipMemcpyDeviceToHost));
+    long long st[8];
+    int rc = nk_field_status(ctx, grouped, st, who);
+    if (rc) return rc;
+    for (size_t b = 0; b < nl; ++b) {
+        if (N) N[b] = a[5 * b];
+        if (E) E[b] = a[5 * b + 1];
+        if (F) { F[3 * b] = a[5 * b + 2]; F[3 * b + 1] = a[5 * b + 3]; F[3 * b + 2] = a[5 * b + 4]; }
+    }
+    if (samples) *samples = st[NK_FIELD_ST_SAMPLES];
+    if (count) *count = st[count_word];
+    if (reset) {
+        NK_HIP(hipMemset(g.acc, 0, a.size() * sizeof(double)));
+        NK_HIP(hipMemset(g.status, 0, (size_t)g.nstatus * sizeof(long long)));
     }
     return NK_OK;
 }
@@ -2235,14 +2237,14 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
         }
         // the field of the same particles on field steps (k_field; one launch per field step whatever the grid size)
         if (ctx->field.on && do_flux && ((stepno + 1) % ctx->field.cfg.every) == 0) {
-            int rcf_ = nk_field_sample(ctx, false);
+            int rcf_ = nk_field_sample(ctx, false, false);
             if (rcf_) return rcf_;
-            NK_HIP(nk_field_accumulate(ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
+            NK_HIP(nk_field_accumulate(ctx->field.g, ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
             // ... and the same sums per (cell, group of modes): taken or dropped with the field's sample
             if (ctx->fgroups.on) {
-                int rcg_ = nk_fgroups_sample(ctx, false);
+                int rcg_ = nk_field_sample(ctx, true, false);
                 if (rcg_) return rcg_;
-                NK_HIP(nk_fgroups_accumulate(ctx->fgroups, ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
+                NK_HIP(nk_field_accumulate(ctx->fgroups.g, ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
             }
         }
         // the mode-resolved tally of the same particles on mode steps (k_modes: one wave per segment)
@@ -2651,12 +2653,12 @@ static int nk_step_end(nk_ctx *ctx, int overflow) {
         if ((rc = nk_comm_allreduce(ctx, ctx->band_rows.data(), (int64_t)ctx->band_rows.size()))) return rc;
     }
     if (ctx->field.on) {
-        long long st[4];
-        rc = nk_field_status(ctx, st, "nk_step");
+        long long st[8];
+        rc = nk_field_status(ctx, false, st, "nk_step");
         if (ctx->fgroups.on) {                           // (both are read, so that neither keeps a stale overflow for the next call)
             const std::string ef = ctx->err;
             long long sg[8];
-            const int rcg = nk_fgroups_status(ctx, sg, "nk_step");
+            const int rcg = nk_field_status(ctx, true, sg, "nk_step");
             if (rc && rcg == NK_ERR_CAPACITY) ctx->err = ef + "; " + ctx->err;
             else if (rc) ctx->err = ef;
             if (!rc) rc = rcg;
@@ -3402,34 +3404,13 @@ int nk_set_field(nk_ctx *ctx, const nk_field *f) {
 
 int nk_get_field(nk_ctx *ctx, double *N, double *E, double *F, int64_t *samples, int64_t *clamped, int32_t reset) {
     NK_ARG(ctx, "nk_get_field: bad arguments");
-    NkFieldHost &fh = ctx->field;
-    NK_ARG(fh.on, "nk_get_field: no field was set (nk_set_field)");
-    NK_HIP(hipSetDevice(ctx->device));
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    const size_t nc = (size_t)fh.ncells;
-    std::vector<double> a(nc * 5);
-    NK_HIP(hipMemcpy(a.data(), fh.acc, a.size() * sizeof(double), hipMemcpyDeviceToHost));
-    long long st[4];
-    int rc = nk_field_status(ctx, st, "nk_get_field");
-    if (rc) return rc;
-    for (size_t c = 0; c < nc; ++c) {
-        if (N) N[c] = a[5 * c];
-        if (E) E[c] = a[5 * c + 1];
-        if (F) { F[3 * c] = a[5 * c + 2]; F[3 * c + 1] = a[5 * c + 3]; F[3 * c + 2] = a[5 * c + 4]; }
-    }
-    if (samples) *samples = st[0];
-    if (clamped) *clamped = st[1];
-    if (reset) {
-        NK_HIP(hipMemset(fh.acc, 0, a.size() * sizeof(double)));
-        NK_HIP(hipMemset(fh.status, 0, 4 * sizeof(long long)));
-    }
-    return NK_OK;
+    NK_ARG(ctx->field.on, "nk_get_field: no field was set (nk_set_field)");
+    return nk_field_get(ctx, false, "nk_get_field", N, E, F, samples, clamped, NK_FIELD_ST_CLAMPED, reset);
 }
 
-int nk_tally_field_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped) {
-    NK_ARG(ctx && raw, "nk_tally_field_state: bad arguments");
-    NkFieldHost &fh = ctx->field;
-    NK_ARG(fh.on, "nk_tally_field_state: no field was set (nk_set_field)");
+// The raw integers of the state as it is now, of either grid: [lines][8], and the header's counts.  The ready check, the
+// normalisation and the deferred relaxation of every state-mode tally, then refresh, one pass, copy-out, clear, header check.
+static int nk_field_tally_state(nk_ctx *ctx, bool grouped, const char *who, int64_t *raw, int64_t *clamped, int64_t *ungrouped) {
     int rc = nk_check_ready(ctx);
     if (rc) return rc;
     NK_HIP(hipSetDevice(ctx->device));
@@ -3440,21 +3421,29 @@ int nk_tally_field_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped) {
         ctx->pending_relax = false;
     }
     if ((rc = nk_field_refresh(ctx))) return rc;
-    if ((rc = nk_field_sample(ctx, true))) return rc;
-    const size_t nc = (size_t)fh.ncells;
-    std::vector<int64_t> h((nc + 1) * 8);
-    NK_HIP(hipMemcpyAsync(h.data(), fh.grid, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    NK_HIP(nk_field_clear_grid(fh, ctx->stream));
+    if (grouped && (rc = nk_fgroups_refresh(ctx))) return rc;
+    if ((rc = nk_field_sample(ctx, grouped, true))) return rc;
+    NkFieldGrid &g = nk_field_grid(ctx, grouped);
+    const size_t nl = (size_t)g.lines;
+    std::vector<int64_t> h((nl + 1) * 8);
+    NK_HIP(hipMemcpyAsync(h.data(), g.grid, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(nk_field_clear_grid(g, ctx->stream));
     NK_HIP(hipStreamSynchronize(ctx->stream));
-    const int64_t *hdr = h.data() + nc * 8;
-    if (hdr[1] || hdr[2]) {
-        ctx->err = "nk_tally_field_state: field overflow: " + std::to_string((long long)hdr[1]) + " term(s) of E above B_E = " +
-                   std::to_string(fh.BE) + " eV, " + std::to_string((long long)hdr[2]) + " term(s) of F above B_F = " + std::to_string(fh.BF);
+    const int64_t *hdr = h.data() + nl * 8;
+    if (hdr[NK_FIELD_OVE] || hdr[NK_FIELD_OVF]) {
+        ctx->err = nk_field_overflow(ctx, grouped, who, (long long)hdr[NK_FIELD_OVE], (long long)hdr[NK_FIELD_OVF]) + (grouped ? NK_FIELD_LEFT_OUT : "");
         return NK_ERR_CAPACITY;
     }
-    memcpy(raw, h.data(), nc * 8 * sizeof(int64_t));
-    if (clamped) *clamped = hdr[0];
+    memcpy(raw, h.data(), nl * 8 * sizeof(int64_t));
+    if (clamped) *clamped = hdr[NK_FIELD_CLAMPED];
+    if (ungrouped) *ungrouped = hdr[NK_FIELD_UNGROUPED];
     return NK_OK;
+}
+
+int nk_tally_field_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped) {
+    NK_ARG(ctx && raw, "nk_tally_field_state: bad arguments");
+    NK_ARG(ctx->field.on, "nk_tally_field_state: no field was set (nk_set_field)");
+    return nk_field_tally_state(ctx, false, "nk_tally_field_state", raw, clamped, nullptr);
 }
 
 int nk_field_info(nk_ctx *ctx, nk_field_report *out) {
@@ -3468,8 +3457,8 @@ int nk_field_info(nk_ctx *ctx, nk_field_report *out) {
     out->k_E = fh.kE; out->k_F = fh.kF;
     out->B_E = fh.BE; out->B_F = fh.BF;
     out->capacity = fh.capacity;
-    out->bytes = fh.bytes;
-    out->lds_path = nk_field_lds_bins(fh, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_field_pass asks, too)
+    out->bytes = fh.g.bytes;
+    out->lds_path = nk_field_lds_bins(fh.g, fh.force_global, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_field_pass asks, too)
     out->on = 1;
     return NK_OK;
 }
@@ -3490,60 +3479,14 @@ int nk_set_field_groups(nk_ctx *ctx, int32_t ngroups, const int32_t *group_of_mo
 
 int nk_get_field_groups(nk_ctx *ctx, double *N, double *E, double *F, int64_t *samples, int64_t *ungrouped, int32_t reset) {
     NK_ARG(ctx, "nk_get_field_groups: bad arguments");
-    NkFGroupsHost &Gh = ctx->fgroups;
-    NK_ARG(Gh.on, "nk_get_field_groups: no groups were set (nk_set_field_groups)");
-    NK_HIP(hipSetDevice(ctx->device));
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    const size_t nl = (size_t)Gh.lines;
-    std::vector<double> a(nl * 5);
-    NK_HIP(hipMemcpy(a.data(), Gh.acc, a.size() * sizeof(double), hipMemcpyDeviceToHost));
-    long long st[8];
-    int rc = nk_fgroups_status(ctx, st, "nk_get_field_groups");
-    if (rc) return rc;
-    for (size_t b = 0; b < nl; ++b) {
-        if (N) N[b] = a[5 * b];
-        if (E) E[b] = a[5 * b + 1];
-        if (F) { F[3 * b] = a[5 * b + 2]; F[3 * b + 1] = a[5 * b + 3]; F[3 * b + 2] = a[5 * b + 4]; }
-    }
-    if (samples) *samples = st[NK_FG_ST_SAMPLES];
-    if (ungrouped) *ungrouped = st[NK_FG_ST_UNGROUPED];
-    if (reset) {
-        NK_HIP(hipMemset(Gh.acc, 0, a.size() * sizeof(double)));
-        NK_HIP(hipMemset(Gh.status, 0, 8 * sizeof(long long)));
-    }
-    return NK_OK;
+    NK_ARG(ctx->fgroups.on, "nk_get_field_groups: no groups were set (nk_set_field_groups)");
+    return nk_field_get(ctx, true, "nk_get_field_groups", N, E, F, samples, ungrouped, NK_FIELD_ST_UNGROUPED, reset);
 }
 
 int nk_tally_field_groups_state(nk_ctx *ctx, int64_t *raw, int64_t *clamped, int64_t *ungrouped) {
     NK_ARG(ctx && raw, "nk_tally_field_groups_state: bad arguments");
-    NkFGroupsHost &Gh = ctx->fgroups;
-    NK_ARG(Gh.on, "nk_tally_field_groups_state: no groups were set (nk_set_field_groups)");
-    int rc = nk_check_ready(ctx);
-    if (rc) return rc;
-    NK_HIP(hipSetDevice(ctx->device));
-    NkDev &d = ctx->d;
-    if ((rc = nk_normalize(ctx))) return rc;
-    if (ctx->pending_relax) {                          // the state the caller means includes the deferred relaxation
-        k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 0);
-        ctx->pending_relax = false;
-    }
-    if ((rc = nk_field_refresh(ctx))) return rc;
-    if ((rc = nk_fgroups_refresh(ctx))) return rc;
-    if ((rc = nk_fgroups_sample(ctx, true))) return rc;
-    const size_t nl = (size_t)Gh.lines;
-    std::vector<int64_t> h((nl + 1) * 8);
-    NK_HIP(hipMemcpyAsync(h.data(), Gh.grid, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    NK_HIP(nk_fgroups_clear_grid(Gh, ctx->stream));
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    const int64_t *hdr = h.data() + nl * 8;
-    if (hdr[NK_FG_OVE] || hdr[NK_FG_OVF]) {
-        ctx->err = nk_fgroups_overflow(ctx, "nk_tally_field_groups_state", (long long)hdr[NK_FG_OVE], (long long)hdr[NK_FG_OVF]);
-        return NK_ERR_CAPACITY;
-    }
-    memcpy(raw, h.data(), nl * 8 * sizeof(int64_t));
-    if (clamped) *clamped = hdr[NK_FG_CLAMPED];
-    if (ungrouped) *ungrouped = hdr[NK_FG_UNGROUPED];
-    return NK_OK;
+    NK_ARG(ctx->fgroups.on, "nk_tally_field_groups_state: no groups were set (nk_set_field_groups)");
+    return nk_field_tally_state(ctx, true, "nk_tally_field_groups_state", raw, clamped, ungrouped);
 }
 
 int nk_field_groups_info(nk_ctx *ctx, nk_field_groups_report *out) {
@@ -3552,9 +3495,9 @@ int nk_field_groups_info(nk_ctx *ctx, nk_field_groups_report *out) {
     const NkFGroupsHost &Gh = ctx->fgroups;
     if (!Gh.on) return NK_OK;
     out->G = Gh.G;
-    out->lines = Gh.lines;
-    out->bytes = Gh.bytes;
-    out->lds_path = nk_fgroups_lds_bins(Gh, ctx->field, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_fgroups_pass asks, too)
+    out->lines = Gh.g.lines;
+    out->bytes = Gh.g.bytes;
+    out->lds_path = nk_field_lds_bins(Gh.g, ctx->field.force_global, nk_lds(ctx, false)) ? 1 : 0;      // (what nk_field_pass asks, too)
     out->k_E = ctx->field.kE; out->k_F = ctx->field.kF;
     out->permutes = Gh.permutes;
     out->on = 1;

@@ -2168,166 +2168,6 @@ NK_KERNEL_LINKAGE __global__ __launch_bounds__(256) void k_spectral_reduce(const
     }
 }
 
-// =================================================================================== spatial field maps
-// The reference shows WHERE the heat goes with a scatter of every particle (Population.plot_figures, Population.py:1841-1979,
-// called at :123 and every 100 steps at :1735).  The engine's counterpart is a field: a uniform grid lo / h / n over the
-// geometry's bounding box, independent of the subvolumes, with five sums per cell -- N (particles), E = sum e, F = sum v e.
-// k_field is a pass of its own over the store, which it only reads, with the two modes of k_spectral:
-//   STATE = false (step mode): right after the sweep of a field step (and k_events_end / k_deliver); e = nk_tally_e against
-//     the subvolume temperatures the sweep used, so the cells and the step's history row are sums of the same terms.
-//   STATE = true: a snapshot, e against the occupation at the particle's interpolated temperature, as k_spectral<true>.
-// Cell (ix, iy, iz), ix = floor((x - lo_x) * inv_h_x); an index outside [0, n) is CLAMPED into the edge cell (the store holds
-// particles a hair outside the box: just behind a reservoir face, escapees waiting for contains_check -- the slice classifier
-// puts those into the end slices too) and counted in the header's `clamped`.
-// The sums are 64-BIT INTEGERS: every real term is scaled by a power of two (sE for e, sF for v e: the host's 2^k_E, 2^k_F,
-// nk_field.hip), rounded to nearest (rint) and added as int64 in two's complement.  Integer adds commute, so a field is the
-// same bits from run to run, for any grid of workgroups, on either path below, and on any split of the particles over ranks.
-// A term above its bound (B_E, B_F) is NOT added: it raises the header's overflow counts and the host reports it.
-// Grid memory: one 64-byte line of 8 words per cell {N, E, Fx, Fy, Fz, -, -, -}, cell (ix * ny + iy) * nz + iz, so that a
-// particle's five adds touch one line; line `ncells` is the header {clamped, overflow E, overflow F, ran, skip, -, -, -}.
-//   lds_bins = 1: the whole grid fits the launch's LDS (behind the subvolume tables, at byte offset lds0): {E, Fx, Fy, Fz}
-//     (u64) and N (u32) per cell there, integer LDS adds, and one flush of integer global adds per workgroup (non-zero bins);
-//   lds_bins = 0: the adds go to global memory directly.  Same integers either way.
-// The only global atomics are 64-bit integer adds (global_atomic_add_x2, no compare-and-swap loop); the store is read once
-// per launch whatever the grid size.
-struct NkFieldDev {
-    double lo[3], inv_h[3];
-    int32_t n[3], ncells;
-    double sE, sF;                    // 2^k_E, 2^k_F
-    double BE, BF;                    // bounds of |e| and of |v e| (every component)
-    unsigned long long *grid;         // [(ncells + 1) * 8]
-    int32_t lds_bins, lds0;
-};
-#define NK_FIELD_WG 1024
-__device__ __forceinline__ int nk_field_axis(double x, double lo, double inv_h, int n, bool &clamped) {
-    const double f = floor((x - lo) * inv_h);
-    if (!(f >= 0.0)) { clamped = true; return 0; }                  // (also a NaN coordinate)
-    if (f >= (double)n) { clamped = true; return n - 1; }
-    return (int)f;
-}
-template <bool STATE>
-__global__ __launch_bounds__(NK_FIELD_WG) void k_field(NkDev d, NkFieldDev f) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    if (!STATE && d.halt[0]) return;                 // a halted batch: the sweep did nothing at this step
-    NkLds L;
-    nk_lds_setup<0, 0>(d, smem, L);
-    const int nc = f.ncells;
-    unsigned long long *bR = (unsigned long long *)(smem + f.lds0);     // [4 nc] E, Fx, Fy, Fz of cell c at 4 c
-    unsigned int *bN = (unsigned int *)(bR + 4 * (size_t)nc);            // [nc]
-    if (f.lds_bins) {
-        for (int i = threadIdx.x; i < 4 * nc; i += blockDim.x) bR[i] = 0ull;
-        for (int i = threadIdx.x; i < nc; i += blockDim.x) bN[i] = 0u;
-        __syncthreads();
-    }
-    unsigned long long *hdr = f.grid + (size_t)nc * 8;
-    unsigned int n_clamped = 0, n_ovE = 0, n_ovF = 0, stuck = 0;
-    const uint32_t lbmask = (1u << d.lb) - 1u;
-    for (int seg = blockIdx.x; seg < d.nseg; seg += gridDim.x) {
-        const int64_t base = (int64_t)seg * d.segcap + (d.seg_lo ? d.seg_lo[seg] : 0);
-        const int count = d.seg_count[seg];
-        // step mode: migrants that k_deliver could not place wait in the inbox -- the sweep tallied particles this pass
-        // cannot see, so the sample is dropped (header `skip`)
-        if (!STATE && d.mig_buf && threadIdx.x == 0 && d.mig_n[seg] > 0) stuck = 1;
-        const NkSegModes sm = nk_seg_modes(d, seg);
-        for (int k = threadIdx.x; k < count; k += blockDim.x) {
-            const int64_t i = base + k;
-            const int idx = (int)(d.w0[i] & lbmask);
-            const NkMode *rec = sm.rec + idx;
-            const double x = d.x[i], y = d.y[i], z = d.z[i];
-            double e;
-            if (STATE) {
-                double invT;
-                const double T = nk_interp_T(d, L.tb, x, y, z, invT);
-                const double n0 = !d.T_ref_local ? nk_occupation(d, d.T_ref, rec->omega, rec->E0)
-                                                 : (T > 0.0 ? nk_be(rec->omega * d.c_hk, rec->E0, invT, d.invT0) : 0.0);
-                e = d.hbar * rec->omega * (d.occ[i] - n0);
-            } else {
-                const int s = nk_classify(d, L.tb, x, y, z);
-                e = nk_tally_e(d, L.tb, s, d.occ[i], rec->omega, rec->E0);
-            }
-            bool cl = false;
-            const int ix = nk_field_axis(x, f.lo[0], f.inv_h[0], f.n[0], cl);
-            const int iy = nk_field_axis(y, f.lo[1], f.inv_h[1], f.n[1], cl);
-            const int iz = nk_field_axis(z, f.lo[2], f.inv_h[2], f.n[2], cl);
-            n_clamped += cl ? 1u : 0u;
-            const int c = (ix * f.n[1] + iy) * f.n[2] + iz;
-            const double fx = rec->vx * e, fy = rec->vy * e, fz = rec->vz * e;
-            const bool okE = fabs(e) <= f.BE;                                     // (false for a NaN as well)
-            const bool okF = fabs(fx) <= f.BF && fabs(fy) <= f.BF && fabs(fz) <= f.BF;
-            n_ovE += okE ? 0u : 1u;
-            n_ovF += okF ? 0u : 1u;
-            const unsigned long long qE = okE ? (unsigned long long)(long long)rint(e * f.sE) : 0ull;
-            const unsigned long long qx = okF ? (unsigned long long)(long long)rint(fx * f.sF) : 0ull;
-            const unsigned long long qy = okF ? (unsigned long long)(long long)rint(fy * f.sF) : 0ull;
-            const unsigned long long qz = okF ? (unsigned long long)(long long)rint(fz * f.sF) : 0ull;
-            if (f.lds_bins) {
-                atomicAdd(bN + c, 1u);
-                atomicAdd(bR + 4 * c + 0, qE);
-                atomicAdd(bR + 4 * c + 1, qx);
-                atomicAdd(bR + 4 * c + 2, qy);
-                atomicAdd(bR + 4 * c + 3, qz);
-            } else {
-                unsigned long long *g = f.grid + (size_t)c * 8;
-                atomicAdd(g + 0, 1ull);
-                atomicAdd(g + 1, qE);
-                atomicAdd(g + 2, qx);
-                atomicAdd(g + 3, qy);
-                atomicAdd(g + 4, qz);
-            }
-        }
-    }
-    if (n_clamped) atomicAdd(hdr + 0, (unsigned long long)n_clamped);
-    if (n_ovE) atomicAdd(hdr + 1, (unsigned long long)n_ovE);
-    if (n_ovF) atomicAdd(hdr + 2, (unsigned long long)n_ovF);
-    if (stuck) atomicAdd(hdr + 4, 1ull);
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(hdr + 3, 1ull);           // this rank's pass ran
-    if (f.lds_bins) {
-        __syncthreads();
-        for (int c = threadIdx.x; c < nc; c += blockDim.x) {
-            const unsigned int n = bN[c];
-            if (n == 0u) continue;
-            unsigned long long *g = f.grid + (size_t)c * 8;
-            atomicAdd(g + 0, (unsigned long long)n);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const unsigned long long v = bR[4 * c + k]; if (v) atomicAdd(g + 1 + k, v); }
-        }
-    }
-}
-// One sample's integer grid into the time average, in cell order: acc[c][5] += grid[c][0..4] / {1, sE, sF, sF, sF} (doubles;
-// the headroom of the integers is spent per sample, not per window), then the grid is cleared for the next sample.  With a
-// communicator the grid has been all-reduced (integers, sum) first, so every rank adds the same numbers.  The sample counts
-// only if the pass ran on every rank (header `ran` = nranks: not in a halted batch) and no rank saw undelivered migrants
-// (`skip` = 0).  (A template, like k_field, so that only the translation unit that launches it compiles it: nk_field.hip.)
-template <int NK_TU = 0>
-__global__ __launch_bounds__(256) void k_field_accum(NkFieldDev f, double *acc, int nranks) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= f.ncells) return;
-    const unsigned long long *hdr = f.grid + (size_t)f.ncells * 8;
-    const bool take = hdr[3] == (unsigned long long)nranks && hdr[4] == 0ull;
-    unsigned long long *g = f.grid + (size_t)c * 8;
-    if (take) {
-        const double iE = 1.0 / f.sE, iF = 1.0 / f.sF;
-        double *a = acc + (size_t)c * 5;
-        a[0] += (double)(long long)g[0];
-        a[1] += (double)(long long)g[1] * iE;
-        a[2] += (double)(long long)g[2] * iF;
-        a[3] += (double)(long long)g[3] * iF;
-        a[4] += (double)(long long)g[4] * iF;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) g[k] = 0ull;
-}
-// ... and the header into the running status {samples, clamped, overflow E, overflow F}; the header is cleared.
-template <int NK_TU = 0>
-__global__ void k_field_finish(NkFieldDev f, long long *status, int nranks) {
-    unsigned long long *hdr = f.grid + (size_t)f.ncells * 8;
-    const bool take = hdr[3] == (unsigned long long)nranks && hdr[4] == 0ull;
-    if (take) { status[0] += 1; status[1] += (long long)hdr[0]; }
-    status[2] += (long long)hdr[1];
-    status[3] += (long long)hdr[2];
-    for (int k = 0; k < 8; ++k) hdr[k] = 0ull;
-}
-
 // =================================================================================== mode-resolved tally
 // The solution itself: E[m][s] = sum e_i and N[m][s] over the particles of subvolume s in mode m = q * J + j, at full
 // resolution (M x S bins: 3.6 million at BASELINE config 2).  A pass of its own over the store, which it only reads, with the

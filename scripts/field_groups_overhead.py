@@ -1,4 +1,4 @@
-"""Cost of the grouped field maps (k_field_groups, nk_set_field_groups): BASELINE config 2 at full size.
+"""Cost of the grouped field maps (k_field<STATE, true>, nk_set_field_groups): BASELINE config 2 at full size.
 
     python scripts/field_groups_overhead.py [--particles 1e7] [--reps 5] [--out profiles/r09_field_groups_overhead.txt]
 
@@ -9,7 +9,7 @@ sees the same store placement; every repeat is listed.
 
 --profile: instead, a short run for a kernel trace (rocprofv3 --kernel-trace --stats -- python scripts/field_groups_overhead.py
 --profile): the slab grid with 100 frequency groups and 100 frequency bands at every = 10 for 30 steps, a few nk_tally_state
-calls, then 64^3 x 8 groups for 30 steps -- k_field_groups, k_field, k_spectral and k_tally_state timed in one run on one store.
+calls, then 64^3 x 8 groups for 30 steps -- the grouped and the plain k_field, k_spectral and k_tally_state timed in one run on one store.
 """
 import argparse
 import json

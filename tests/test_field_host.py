@@ -1,8 +1,12 @@
 """Host side of the spatial field maps (nanokappa_amd/field.py; no GPU): the float64 sums against an independent histogram of
 the reference's own frozen-step particles, slice-aligned grids against the golden subvolume sums, the quantised sums, the
-normalisations against the golden subvolume energies and temperatures, VTK round trip and the --field_grid option."""
+normalisations against the golden subvolume energies and temperatures, VTK round trip and the --field_grid option; and the shape of the field kernels' machine code."""
 import os
+import re
+import shutil
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -177,3 +181,67 @@ def test_field_grid_option_and_parser(capsys):
     assert FD.field_grid_option(p.parse_args(req + ['--field_grid', '16', '16', '32', '50']).field_grid) == ((16, 16, 32), 50)
     a = p.parse_args(req + ['--fig_plot', 'T', 'e'])               # still accepted
     assert a.fig_plot == ['T', 'e'] and a.field_grid == []
+
+
+# ---------------------------------------------------------------------------------------------- the shape of the kernels
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+_ASM = {}
+# VGPRs of k_field<STATE, GROUPED> when the plain and the grouped kernel were two: the merged kernel must not need more
+VGPR_CAP = {(False, False): 45, (True, False): 54, (False, True): 49, (True, True): 58}
+
+
+def _assembly():
+    """nk_field.hip compiled to gfx950 assembly with the flags of nanokappa_amd/csrc/Makefile (CXXFLAGS); no GPU needed."""
+    if 'text' not in _ASM:
+        assert os.path.exists(HIPCC), 'hipcc is required here: the check is part of the build'
+        tmp = tempfile.mkdtemp()
+        try:
+            out = os.path.join(tmp, 'nk_field.s')
+            subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-mllvm', '-disable-machine-licm',
+                                   '--cuda-device-only', '-S', '-o', out, os.path.join(ROOT, 'nanokappa_amd', 'csrc', 'nk_field.hip')],
+                                  stderr=subprocess.DEVNULL)
+            _ASM['text'] = open(out).read()
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+    return _ASM['text']
+
+
+def _kernel_name(state, grouped):
+    return '_Z7k_fieldILb%dELb%dEEv5NkDev10NkFieldDev' % (int(state), int(grouped))
+
+
+def _kernel(text, name):
+    lines = text.split('\n')
+    a = next((i for i, l in enumerate(lines) if l.startswith(name + ':')), None)
+    assert a is not None, 'kernel %s not found in the assembly' % name
+    b = next(i for i in range(a, len(lines)) if '.end_amdhsa_kernel' in lines[i])
+    return [l.split(';')[0].strip() for l in lines[a:b]], '\n'.join(lines[a:b])
+
+
+@pytest.mark.parametrize('state,grouped', sorted(VGPR_CAP))
+def test_kernel_shape(state, grouped):
+    text = _assembly()
+    name = _kernel_name(state, grouped)
+    code, raw = _kernel(text, name)
+    ops = [c.split()[0] for c in code if c and not c.startswith('.') and not c.endswith(':')]
+    assert 'ds_add_u64' in ops and 'ds_add_u32' in ops                      # the LDS path's bins: integer LDS adds
+    assert 'global_atomic_add_x2' in ops                                    # the global path, the flush, the header: integer adds
+    assert not [o for o in ops if 'cmpswap' in o], 'a compare-and-swap loop'
+    fp_atomic = re.compile(r'atomic_(add|pk_add|min|max|fmin|fmax)_(f16|f32|f64|bf16)|ds_(add|min|max|pk_add)_(rtn_)?(f16|f32|f64|bf16)')
+    assert not [o for o in ops if fp_atomic.search(o)], 'a floating-point atomic'
+    # no scratch: a spilled register in a streaming loop is reloaded through the same in-order queue as the next loads
+    assert not [o for o in ops if o.startswith('scratch_') or o.startswith('buffer_') and 'offen' in o]
+    assert re.search(r'\.amdhsa_private_segment_fixed_size 0\b', raw), 'the kernel uses scratch memory'
+    meta = re.search(r'\.name:\s+%s\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)' % re.escape(name), text)
+    assert meta is None or int(meta.group(1)) == 0
+    vgprs = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', raw).group(1))
+    print('%s: %d VGPRs (cap %d)' % (name, vgprs, VGPR_CAP[state, grouped]))
+    assert vgprs <= VGPR_CAP[state, grouped]
+
+
+def test_only_the_field_kernels_are_in_the_translation_unit():
+    text = _assembly()
+    names = set(re.findall(r'^\s*\.amdhsa_kernel\s+(\S+)', text, flags=re.M))
+    want = {_kernel_name(s, g) for s, g in VGPR_CAP} | {'_Z13k_field_accumPyiddPdi', '_Z14k_field_finishPyiPxii', '_Z15k_field_permutePKiS0_Pili'}
+    assert names == want, names ^ want

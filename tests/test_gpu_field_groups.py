@@ -1,4 +1,4 @@
-"""Grouped field maps on the GPU (nk_set_field_groups / k_field_groups): the sums over the groups against the field's own
+"""Grouped field maps on the GPU (nk_set_field_groups / k_field<., true>): the sums over the groups against the field's own
 integers, state mode against the host restatement, step mode against the oracle's particles, a slab grid against the band rows
 of k_spectral, the two paths, a store that regrows in mid-window, degenerate shapes, errors and lifetime, a one-rank
 communicator and the Population outputs (field_groups.npz)."""
@@ -235,6 +235,32 @@ def test_large_grid_takes_the_global_path():
     eng.step(10)
     assert_windows_add_up(eng.field(), eng.field_groups())
     assert_groups_add_up_to_field(eng, '(16^3 x 8)')
+
+
+def test_field_and_groups_choose_their_paths_independently():
+    """One engine, one host path for both grids: 16 x 16 x 8 = 2048 cells are 72 KB of LDS bins (above the 64 KB a kernel may
+    have without being allowed more, below the 160 KB limit), so the field takes the LDS path; with G = 2 the 4096 lines are
+    144 KB -- the LDS path too, with a larger allowance of its own; with G = 8 the 16384 lines do not fit and the groups go
+    global while the field stays in LDS.  In either setting the groups' integers add up to the field's, bit for bit."""
+    ct = case_tables('ttp')
+    pop4 = random_population(ct, 20000, seed=25, T0=303.0)
+    table, G = table_all(ct['M'], 2)
+    eng, _ = engine_with_groups(ct, pop4, table, G, n=(16, 16, 8))
+    for G, paths in ((2, (1, 1)), (8, (1, 0))):
+        if G != 2:
+            eng.set_field_groups(*table_all(ct['M'], G))
+            eng.field(reset=True)                                           # both windows start here
+        fi, gi = eng.field_info(), eng.field_groups_info()
+        print('G = %d: lds_path field %d, groups %d; %d cells, %d lines' % (G, fi['lds_path'], gi['lds_path'], fi['ncells'], gi['lines']))
+        assert fi['ncells'] == 2048 and gi['lines'] == 2048 * G and gi['G'] == G
+        assert (fi['lds_path'], gi['lds_path']) == paths
+        assert_groups_add_up_to_field(eng, 'G = %d, before stepping' % G)
+        eng.step(20)
+        f, g = eng.field(), eng.field_groups()
+        assert f['samples'] == 2
+        assert_windows_add_up(f, g, 'G = %d' % G)
+        assert g['N'].sum() == f['N'].sum() > 0 and np.count_nonzero(g['N'].sum(axis=(0, 1, 2))) == G
+        assert_groups_add_up_to_field(eng, 'G = %d, after 20 steps' % G)
 
 
 # ---------------------------------------------------------------------------------------------- 6. a store that regrows
