@@ -345,6 +345,29 @@ typedef struct {
 } nk_field_groups_report;
 int nk_field_groups_info(nk_ctx *ctx, nk_field_groups_report *out);
 
+/* ---- Solid fraction of the field's cells.  A set-up helper of the host geometry (no context), as nk_mesh_crossings: V[c],
+ * the volume of solid in cell c = (ix * n[1] + iy) * n[2] + iz of the grid lo / h / n (the convention of nk_field), for a closed
+ * triangle mesh whose faces are wound so that their normals point out of the solid (tri: three vertices per face).  Exact
+ * for the triangles -- no sampling, no quadrature: every triangle is clipped to the cells of its bounding box, the clipped
+ * polygon gives the signed area a of its projection on the yz plane and p = the integral of (x - x_lo) over it, both summed
+ * per cell as 64-bit integers (scaled by 2^k_A, 2^k_P, rounded to nearest; the same bits from call to call), and
+ * V[ix] = P[ix] + h_x sum_{ix' > ix} A[ix'] along x in every (iy, iz) column.  The arithmetic is done in grid units
+ * (x - lo) / h, so the scales stand for areas and volumes in cells.  A triangle is offered to the cells floor((x - lo) / h) of
+ * its bounding box, clamped into [0, n), and clipped against closed slabs: a face lying in a grid plane perpendicular to x is
+ * counted in exactly one cell, one in the grid's upper x boundary in the last cell.  The grid must contain the bounding box of
+ * the triangles and may be larger (cells outside the solid get 0); a vertex within 1e-9 cells outside it (rounding of a grid
+ * made from the mesh's own bounds) is moved onto the boundary.  nanokappa_amd.field.solid_volume is the same rule in NumPy.
+ * NK_ERR_ARG, with a text that names the cause (nk_solid_last_error): n_faces <= 0, h <= 0, more than 2^24 cells, a grid
+ * that does not contain the triangles; NK_ERR_NODEVICE without a gfx950 device. */
+typedef struct {
+    int64_t ncells, pairs;   /* cells; (triangle, yz column) work items of the clipping kernel */
+    int32_t k_A, k_P;        /* the integers hold a 2^k_A and p 2^k_P (a, p in grid units) */
+    double seconds;          /* device time of the two kernels */
+} nk_solid_report;
+int nk_cell_solid_volume(int device, int64_t n_faces, const double *tri /* [n_faces*9], outward */, const double lo[3],
+                         const double h[3], const int32_t n[3], double *V /* [ncells] */, nk_solid_report *rep /* may be NULL */);
+const char *nk_solid_last_error(void);               /* text of this thread's last failed nk_cell_solid_volume */
+
 /* Mode-resolved tally: the distribution itself, E[s][m] = sum e_i and N[s][m] over the particles of subvolume s in mode
  * m = q*J + j, at full resolution (S x M bins).  The group velocity is a property of the mode, so the heat flux of a mode is
  * v_m E[s][m] exactly, and any band sum of nk_set_bands is a sum of entries of this table.  One pass over the store per mode

@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups` and `--mode_tally`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid` and `--mode_tally`."""
 import argparse
 import os
 import sys
@@ -61,6 +61,10 @@ def initialise_parser(debug_flag=False):
            'write field_groups.npz; kind = frequency (G bins), branch (one group per branch), mfp (G log-spaced bins of the '
            'mean free path at the mean reservoir temperature) or direction (G bins of the cosine between the group velocity '
            'and the axis x|y|z, default the slice axis); off by default')
+    a('--field_solid', action='store_true', default=False,
+      help='with --field_grid: compute the exact solid fraction of every grid cell on the GPU, once; --energy_normal fixed '
+           'then divides by the volume of solid in a cell instead of the whole cell (cells cut by the surface read right), '
+           'and field.vtk / field_groups.npz carry solid_fraction; off by default')
     a('--mode_tally', default=['0'], type=str, nargs='*',
       help='[every]: tally energy and particle count per (subvolume, mode) every `every` steps (default 100, a multiple of '
            'n_dt_to_conv = 10) on the GPU over the convergence window, and write mode_tally.npz and the conductivity '

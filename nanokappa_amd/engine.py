@@ -91,7 +91,8 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_tally_bands_state', 'nk_set_field', 'nk_get_field', 'nk_tally_field_state', 'nk_field_info',
            'nk_set_field_groups', 'nk_get_field_groups', 'nk_tally_field_groups_state', 'nk_field_groups_info',
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
-           'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error']
+           'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
+           'nk_cell_solid_volume', 'nk_solid_last_error']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -116,6 +117,10 @@ class nk_modes(C.Structure):
 class nk_modes_report(C.Structure):
     _fields_ = [('every', C.c_int32), ('k_E', C.c_int32), ('B_E', C.c_double), ('capacity', C.c_int64), ('bytes', C.c_int64),
                 ('owner_path', C.c_int32), ('on', C.c_int32)]
+
+
+class nk_solid_report(C.Structure):
+    _fields_ = [('ncells', C.c_int64), ('pairs', C.c_int64), ('k_A', C.c_int32), ('k_P', C.c_int32), ('seconds', C.c_double)]
 
 
 class nk_group_report(C.Structure):
@@ -210,6 +215,9 @@ def load_library():
     L.nk_group_info.argtypes = [C.c_void_p, C.POINTER(nk_group_report)]
     L.nk_group_last_error.restype = C.c_char_p
     L.nk_group_last_error.argtypes = [C.c_void_p]
+    L.nk_cell_solid_volume.argtypes = [C.c_int, C.c_int64, c_dp, c_dp, c_dp, c_ip, c_dp, C.POINTER(nk_solid_report)]
+    L.nk_solid_last_error.restype = C.c_char_p
+    L.nk_solid_last_error.argtypes = []
     _lib = L
     return L
 
@@ -239,15 +247,21 @@ def device_count():
     return int(load_library().nk_device_count())
 
 
+def _set_up_device(L, device):
+    """The device of a context-free set-up helper: NK_MESH_DEVICE, else LOCAL_RANK, modulo the devices this process sees."""
+    if device is None:
+        device = int(os.environ.get('NK_MESH_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+        nd = L.nk_device_count()
+        device = device % nd if nd > 0 else 0
+    return int(device)
+
+
 def mesh_crossings(origins, dirs, v0, e1, e2, skip_self=False, device=None):
     """Triangles crossed by every open ray (nk_mesh_crossings; -1 where a ray has too many distinct crossings).
     device: HIP device index; default NK_MESH_DEVICE, else this process's LOCAL_RANK (a rank's geometry set-up stays on the
     rank's own GPU), modulo the devices this process sees."""
     L = load_library()
-    if device is None:
-        device = int(os.environ.get('NK_MESH_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-        nd = L.nk_device_count()
-        device = device % nd if nd > 0 else 0
+    device = _set_up_device(L, device)
     o, d = _d(origins), _d(dirs)
     a, b, c = _d(v0), _d(e1), _d(e2)
     out = np.zeros(o.shape[0], dtype=np.int32)
@@ -255,6 +269,29 @@ def mesh_crossings(origins, dirs, v0, e1, e2, skip_self=False, device=None):
     if rc != 0:
         raise RuntimeError('nk_mesh_crossings failed (%d)' % rc)
     return out
+
+
+def cell_solid_volume(vertices, faces, lo, h, n, device=None, report=False):
+    """Volume of solid in every cell of the grid lo / h / n, (nx, ny, nz) float64, for a closed triangle mesh with outward
+    faces (mesh.Mesh's vertices / faces), exact for the triangles (nk_cell_solid_volume; field.solid_volume is the same rule
+    in NumPy).  device as for mesh_crossings.  report=True: (V, dict ncells, pairs, k_A, k_P, seconds).  NkError, with the
+    library's text, for no faces, h <= 0, more than 2^24 cells or a grid that does not contain the mesh."""
+    L = load_library()
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    tri = _d(v[f]) if f.shape[0] else np.zeros(9)
+    lo3, h3 = _d(np.asarray(lo, dtype=np.float64).reshape(3)), _d(np.asarray(h, dtype=np.float64).reshape(3))
+    n3 = _i(np.asarray(n).reshape(3))
+    nc = int(n3[0]) * int(n3[1]) * int(n3[2])
+    V = np.zeros(nc if 0 < nc <= (1 << 24) and int(n3.min()) > 0 else 1)        # (a bad grid is refused before V is touched)
+    rep = nk_solid_report()
+    rc = L.nk_cell_solid_volume(_set_up_device(L, device), f.shape[0], _p(tri), _p(lo3), _p(h3), _p(n3, c_ip), _p(V), C.byref(rep))
+    if rc != 0:
+        raise NkError('nk_cell_solid_volume failed (%d): %s' % (rc, L.nk_solid_last_error().decode()))
+    V = V.reshape(tuple(int(k) for k in n3))
+    if report:
+        return V, dict(ncells=int(rep.ncells), pairs=int(rep.pairs), k_A=int(rep.k_A), k_P=int(rep.k_P), seconds=float(rep.seconds))
+    return V
 
 
 def comm_unique_id():

@@ -187,8 +187,9 @@ def normalise(N, E, F, N_cell, samples, active_modes, QV, eVpsa2_in_Wm2, norm='m
     """field.normalise per (cell, group).  The scale of a cell is computed from the cell's TOTAL count N_cell (nx, ny, nz) --
     the field's N -- and applied to every group of the cell, so the groups' energies and heat fluxes add up to the field's
     deviational energy and heat flux (for a table without ungrouped modes).  No reference energy is added: a group holds a
-    share of the deviation.  Returns dict N (mean count per sample), energy (eV/angstrom^3), heat_flux (W/m^2); cells without
-    particles are NaN."""
+    share of the deviation.  For 'fixed', cell_volume is the whole cell's volume or, as in field.normalise, an array (nx, ny, nz)
+    with the volume of solid in every cell (a cell of zero volume gives NaN).  Returns dict N (mean count per sample), energy
+    (eV/angstrom^3), heat_flux (W/m^2); cells without particles are NaN."""
     N = np.asarray(N, dtype=np.float64)
     E = np.asarray(E, dtype=np.float64)
     F = np.asarray(F, dtype=np.float64)
@@ -198,7 +199,9 @@ def normalise(N, E, F, N_cell, samples, active_modes, QV, eVpsa2_in_Wm2, norm='m
         if norm == 'fixed':
             if particle_density is None or cell_volume is None:
                 raise ValueError("normalise: 'fixed' needs particle_density and cell_volume")
+            FD.check_cell_volume(cell_volume, Nc.shape)
             scale = np.where(Nc > 0, active_modes / (particle_density * cell_volume * s), np.nan)
+            scale = FD.mask_empty_volume(scale, cell_volume, Nc.shape)
         elif norm == 'mean':
             scale = np.where(Nc > 0, active_modes / Nc, np.nan)
         else:
@@ -212,20 +215,25 @@ def normalise(N, E, F, N_cell, samples, active_modes, QV, eVpsa2_in_Wm2, norm='m
 _KEYS = ('lo', 'h', 'n', 'kind', 'edges', 'N', 'E', 'F', 'heat_flux', 'samples', 'step')
 
 
-def write_field_groups(path, lo, h, n, kind, edges, N, E, F, heat_flux, samples, step):
+def write_field_groups(path, lo, h, n, kind, edges, N, E, F, heat_flux, samples, step, solid_fraction=None):
     """field_groups.npz: the grid (lo, h, n), the kind of the groups and their edges, the window's sums N, E (nx, ny, nz, G),
-    F (.., 3), the normalised heat_flux (W/m^2), the number of samples in the sums and the step."""
+    F (.., 3), the normalised heat_flux (W/m^2), the number of samples in the sums and the step; where given, the solid
+    fraction of every cell (nx, ny, nz) as one more array."""
+    more = {} if solid_fraction is None else dict(solid_fraction=np.asarray(solid_fraction, dtype=np.float64))
     np.savez(path, lo=np.asarray(lo, dtype=np.float64), h=np.asarray(h, dtype=np.float64), n=np.asarray(n, dtype=np.int64),
              kind=np.asarray(str(kind)), edges=np.asarray(edges, dtype=np.float64), N=np.asarray(N, dtype=np.float64),
              E=np.asarray(E, dtype=np.float64), F=np.asarray(F, dtype=np.float64), heat_flux=np.asarray(heat_flux, dtype=np.float64),
-             samples=np.int64(samples), step=np.int64(step))
+             samples=np.int64(samples), step=np.int64(step), **more)
     return path
 
 
 def read_field_groups(path):
-    """What write_field_groups wrote, as a dict (kind a str, n a tuple, samples and step ints)."""
+    """What write_field_groups wrote, as a dict (kind a str, n a tuple, samples and step ints; solid_fraction where the file
+    holds it)."""
     with np.load(path) as z:
         out = {k: z[k] for k in _KEYS}
+        if 'solid_fraction' in z.files:
+            out['solid_fraction'] = z['solid_fraction']
     out['kind'] = str(out['kind'])
     out['n'] = tuple(int(k) for k in out['n'])
     out['samples'], out['step'] = int(out['samples']), int(out['step'])

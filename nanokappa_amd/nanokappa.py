@@ -47,6 +47,10 @@ def main(argv=None):
         sys.stdout = out
     with open(os.path.join(args.results_folder, 'arguments.txt'), 'w') as f:   # nanokappa.py:38-50
         for key, val in vars(args).items():
+            if isinstance(val, bool):              # a switch (--field_solid): the bare option when on, no line when off
+                if val:
+                    f.write('--%s\n' % key)
+                continue
             f.write('--%s %s\n' % (key, val if isinstance(val, str) else ' '.join(str(i) for i in val)))
     mt = [int(i) for i in re.split('-|:', args.max_sim_time[0])]
     max_time = timedelta(days=mt[0], hours=mt[1], minutes=mt[2], seconds=mt[3])

@@ -194,8 +194,9 @@ class Population(Constants):
         # spatial field maps (--field_grid nx ny nz [every]; off by default): the GPU-native counterpart of --fig_plot's scatter
         self.field_n = None
         fn, fev = FD.field_grid_option(getattr(args, 'field_grid', None))
+        fsolid = FD.field_solid_option(getattr(args, 'field_solid', False), fn)     # (--field_solid; needs --field_grid)
         if fn is not None:
-            self.set_field(fn, fev, geometry)
+            self.set_field(fn, fev, geometry, solid=fsolid)
         elif getattr(args, 'fig_plot', None) and self.rank == 0:
             print('--fig_plot is not drawn by this build; --field_grid nx ny nz [every] writes the same quantities on a grid (field.vtk)')
         # the same sums per (cell, group of modes) (--field_groups G kind [axis]; needs --field_grid)
@@ -290,11 +291,16 @@ class Population(Constants):
                                        self._geo.subvol_connections, v.mean_band_k, v.std_band_k, self.current_timestep)
 
     # ----------------------------------------------------------------------- spatial field maps
-    def set_field(self, n, every=FD.FIELD_EVERY_DEFAULT, geometry=None):
+    def set_field(self, n, every=FD.FIELD_EVERY_DEFAULT, geometry=None, solid=False):
         """Sum N, E, F on a uniform grid of n = (nx, ny, nz) cells over geometry.bounds on every `every`-th step (a multiple of
-        n_dt_to_conv) from here on (Engine.set_field); n = None: off."""
+        n_dt_to_conv) from here on (Engine.set_field); n = None: off.
+        solid (--field_solid): also compute, once for this grid, the exact solid fraction of every cell from the geometry's
+        mesh on the GPU (engine.cell_solid_volume; every rank its own copy, the same bits).  field() then returns
+        solid_fraction and N_outside, 'fixed' normalisation of field() and field_groups() divides by fraction x cell volume,
+        and field.vtk / field_groups.npz carry solid_fraction.  Off: everything is as without the option."""
         geometry = geometry if geometry is not None else self._geo
         self._field_last = None
+        self.field_solid_fraction = None
         self.fgroups_G, self._fgroups_last = 0, None            # (a new field switches the groups off: Engine.set_field)
         if n is None:
             self.engine.set_field((0, 0, 0), (1, 1, 1), (0, 0, 0), 1)
@@ -305,6 +311,11 @@ class Population(Constants):
         self.field_lo, self.field_h, self.field_n = FD.grid_from_bounds(geometry.bounds, n)
         self.field_every = int(every)
         self.engine.set_field(self.field_lo, self.field_h, self.field_n, self.field_every)
+        if solid:
+            from .engine import cell_solid_volume
+            V = cell_solid_volume(geometry.mesh.vertices, geometry.mesh.faces, self.field_lo, self.field_h, self.field_n,
+                                  device=int(getattr(self.args, 'device', [0])[0]))
+            self.field_solid_fraction = V / float(np.prod(self.field_h))
         # The averaging window, in steps on the engine's absolute clock: the field steps of n_mean convergence rows (the window
         # of _Stats), a whole number of them and at least one.  A window ends -- the accumulator is read and restarted --
         # whenever current_timestep is a multiple of it; run() cuts its library calls there, so what a window holds does not
@@ -323,12 +334,25 @@ class Population(Constants):
                 lg.update(N_cell=last['N'], step=int(self.current_timestep))
                 self._fgroups_last = lg
 
+    def _field_cell_volume(self):
+        """What 'fixed' normalisation divides by: the cell's volume, or with solid fractions (set_field(solid=True)) the volume
+        of solid in every cell -- 0 where the fraction is at most field.SOLID_EMPTY (a cell outside the solid, whose terms
+        cancel to rounding): such cells are NaN in the normalised maps."""
+        cv = float(np.prod(self.field_h))
+        fr = getattr(self, 'field_solid_fraction', None)
+        if fr is None:
+            return cv
+        return np.where(fr > FD.SOLID_EMPTY, fr, 0.0) * cv
+
     def field(self):
         """The field, normalised the reference's way per cell (field.normalise): dict N (mean particles per cell and field
         step), energy (eV/angstrom^3), T (K), heat_flux (W/m^2) shaped (nx, ny, nz[, 3]), samples, clamped, lo, h, n.  It is the
         mean over the latest COMPLETE window -- field_window steps, the field steps of n_mean convergence rows, always the
         same number of samples (field_window / every, less the field steps the engine had to skip) -- and, until the first window is complete, over the field steps so far.
-        Cells without particles are NaN."""
+        Cells without particles are NaN.  With solid fractions (set_field(solid=True), --field_solid) also solid_fraction
+        (nx, ny, nz; the engine's numbers) and N_outside, the mean particles per sample in cells outside the solid (fraction at
+        most field.SOLID_EMPTY: particles a hair outside the surface, waiting for the contains check), and 'fixed' divides by
+        the volume of solid in a cell, not by the whole cell."""
         if self.field_n is None:
             raise RuntimeError('field: no grid (--field_grid or Population.set_field)')
         raw = self._field_last if self._field_last is not None else self.engine.field()
@@ -342,9 +366,12 @@ class Population(Constants):
             ref = np.full(cen.shape[0], float(self.ref_en_density))
         out = FD.normalise(raw['N'], raw['E'], raw['F'], raw['samples'], ph.number_of_active_modes,
                            ph.number_of_qpoints * ph.volume_unitcell, self.eVpsa2_in_Wm2, norm=self.norm,
-                           particle_density=self.particle_density, cell_volume=float(np.prod(self.field_h)),
+                           particle_density=self.particle_density, cell_volume=self._field_cell_volume(),
                            ref_energy=ref.reshape(self.field_n), temperature_function=ph.temperature_function)
         out.update(samples=raw['samples'], clamped=raw['clamped'], lo=self.field_lo, h=self.field_h, n=self.field_n)
+        fr = getattr(self, 'field_solid_fraction', None)
+        if fr is not None:
+            out.update(solid_fraction=fr, N_outside=float(out['N'][fr <= FD.SOLID_EMPTY].sum()))
         return out
 
     def write_field(self):
@@ -355,7 +382,7 @@ class Population(Constants):
             return None
         return FD.write_vtk(FD.field_path(self.results_folder_name), f['lo'], f['h'], f['n'], f['N'], f['T'], f['energy'],
                             f['heat_flux'], title='nanokappa field: mean over %d field steps up to timestep %d'
-                            % (f['samples'], self.current_timestep))
+                            % (f['samples'], self.current_timestep), solid_fraction=f.get('solid_fraction'))
 
     # ----------------------------------------------------------------------- grouped field maps
     def set_field_groups(self, kind, G, axis=None, phonon=None):
@@ -408,10 +435,13 @@ class Population(Constants):
         ph = self._ph
         nm = FG.normalise(raw['N'], raw['E'], raw['F'], raw['N_cell'], raw['samples'], ph.number_of_active_modes,
                           ph.number_of_qpoints * ph.volume_unitcell, self.eVpsa2_in_Wm2, norm=self.norm,
-                          particle_density=self.particle_density, cell_volume=float(np.prod(self.field_h)))
-        return dict(N=raw['N'], E=raw['E'], F=raw['F'], heat_flux=nm['heat_flux'], energy=nm['energy'], samples=raw['samples'],
-                    ungrouped=raw['ungrouped'], step=raw['step'], kind=self.fgroups_kind, edges=self.fgroups_edges,
-                    lo=self.field_lo, h=self.field_h, n=self.field_n)
+                          particle_density=self.particle_density, cell_volume=self._field_cell_volume())
+        out = dict(N=raw['N'], E=raw['E'], F=raw['F'], heat_flux=nm['heat_flux'], energy=nm['energy'], samples=raw['samples'],
+                   ungrouped=raw['ungrouped'], step=raw['step'], kind=self.fgroups_kind, edges=self.fgroups_edges,
+                   lo=self.field_lo, h=self.field_h, n=self.field_n)
+        if getattr(self, 'field_solid_fraction', None) is not None:
+            out['solid_fraction'] = self.field_solid_fraction
+        return out
 
     def write_field_groups(self):
         if getattr(self, 'fgroups_G', 0) <= 0 or not self.results_folder_name:
@@ -420,7 +450,8 @@ class Population(Constants):
         if g['samples'] == 0:
             return None
         return FG.write_field_groups(FG.field_groups_path(self.results_folder_name), g['lo'], g['h'], g['n'], g['kind'], g['edges'],
-                                     g['N'], g['E'], g['F'], g['heat_flux'], g['samples'], g['step'])
+                                     g['N'], g['E'], g['F'], g['heat_flux'], g['samples'], g['step'],
+                                     solid_fraction=g.get('solid_fraction'))
 
     # ----------------------------------------------------------------------- mode-resolved tally
     def set_modes(self, every=FD.FIELD_EVERY_DEFAULT):
