@@ -247,6 +247,22 @@ struct NkDev {
     unsigned long long *stamps;       // developer build NK_STAMPS (make stamps): per-wave cycle sums of the sweep's sections
 };
 
+// A history row (one per step: written by the update -- nk_update_body, k_resident --, read by the host):
+// acc[NB] | T_sv[S] | E_sv[S] | flux_valid, row_valid, halt request, overflow mask | the four halt words after this step.
+// The host's names for it; the two kernels spell the same offsets out (with these inlined instead, the compiler allots k_reduce's
+// scalar registers differently: the same code, but not the same bytes).
+struct NkRow {
+    int NB, S;
+    constexpr int T() const { return NB; }
+    constexpr int E() const { return NB + S; }
+    constexpr int flux() const { return NB + 2 * S; }          // this step tallied the heat flux
+    constexpr int valid() const { return NB + 2 * S + 1; }     // this step ran
+    constexpr int halt_req() const { return NB + 2 * S + 2; }
+    constexpr int overflow() const { return NB + 2 * S + 3; }
+    constexpr int halt(int k) const { return NB + 2 * S + 4 + k; }
+    constexpr int width() const { return NB + 2 * S + 8; }
+};
+
 // Offsets of slot i in the double-sized fields (x y z occ nts pid share their block stride) and in the packed words, computed
 // once for a whole particle (hot paths; the fields' operator[] recomputes them per access).
 struct NkSlot { int64_t od, ow; };

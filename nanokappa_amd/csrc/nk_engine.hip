@@ -65,7 +65,6 @@ struct nk_ctx {
     int64_t step = 0;
     bool pending_relax = false;
     int g_sweep = 0;               // persistent grid of k_sweep = rows of `partials`
-    std::vector<int32_t> h_seg_count;
     std::vector<hipEvent_t> evpool;
     int g_sweep_key = -1;              // which k_sweep instantiation g_sweep was sized for
     size_t g_sweep_lds = 0;            //   and with how much LDS per workgroup
@@ -109,11 +108,9 @@ struct nk_ctx {
     void *mig_buf = nullptr, *mig_n = nullptr;   // migration inboxes (rough facets; sized with nseg and segcap)
     double *ep_p = nullptr, *rc_p = nullptr;     // (reservoir, mode) tables in the segments' order (sized with nseg)
     int rm_nseg = 0, rm_nlmax = 0;               // segmentation rc_p was built for (0: the counters live in res_counter)
-    void *pin = nullptr;           // pinned host staging of the history rows + the halt words of a batch
-    size_t pin_bytes = 0;
     int32_t halt_words[4] = {0, 0, 0, 0};
     double *acc = nullptr;         // [NB + 2]: tally columns, then the two halt requests that travel with them
-    double *hist = nullptr;        // [hist_cap][HROW]
+    double *hist = nullptr;        // [hist_cap] history rows (NkRow) in pinned host memory
     int hist_cap = 0;
     nk_params params;
     nk_timing timing;
@@ -160,6 +157,8 @@ struct nk_ctx {
     do {                                                                                               \
         if (!(cond)) { ctx->err = msg; return NK_ERR_ARG; }                                            \
     } while (0)
+#define NK_TRY(call)                                                                                   \
+    do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
 template <class T>
 static int nk_upload(nk_ctx *ctx, const T *src, size_t n, const T **dst, bool particle = false) {
@@ -172,42 +171,37 @@ static int nk_upload(nk_ctx *ctx, const T *src, size_t n, const T **dst, bool pa
     *dst = (const T *)p;
     return NK_OK;
 }
-#define NK_UP(src, n, dst)                                                                             \
-    do { int rc_ = nk_upload(ctx, src, n, dst); if (rc_) return rc_; } while (0)
+#define NK_UP(src, n, dst) NK_TRY(nk_upload(ctx, src, n, dst))
+// One zeroed array of the particle store, registered in ctx->pallocs.
+template <class T>
+static int nk_palloc(nk_ctx *ctx, T *&field, size_t count) {
+    const T *p = nullptr;
+    NK_TRY(nk_upload<T>(ctx, nullptr, count, &p, true));
+    field = (T *)p;
+    return NK_OK;
+}
 
 // The particle fields of a store of `cap` slots (a multiple of 64): ONE allocation cut into blocks of 64 slots, every block
 // x | y | z | occ | [nts] | [pid] | w0 (NkField, nk_device.h; the sweep addresses a block's fields from ONE base pointer at
-// compile-time distances, NkBlock).  (Round 3 also had one plain array per field as a developer layout, NK_LAYOUT=soa: measured
-// equal, removed with the single-base addressing.)  The allocation is registered in ctx->pallocs.
-static inline bool nk_layout_soa() { return false; }
+// compile-time distances, NkBlock).  The allocation is registered in ctx->pallocs.
 // bytes of one particle in the store: x y z occ (+ nts unless it is a box store) (+ pid) + the packed word
 static inline int nk_particle_bytes(bool with_pid, bool with_nts) { return 36 + (with_nts ? 8 : 0) + (with_pid ? 8 : 0); }
 static inline size_t nk_store_bytes(int64_t cap, bool with_pid, bool with_nts) {
     const int64_t nblk = (cap + 63) / 64;
     const int nf = 4 + (with_nts ? 1 : 0) + (with_pid ? 1 : 0);   // 8-byte fields per particle
     const int bd = nf * 64 + 32;                                  // doubles per block (the 64 packed words take 32)
-    const size_t bytes = nk_layout_soa() ? (size_t)nblk * 64 * (nf * 8 + 4) : (size_t)nblk * bd * 8;
+    const size_t bytes = (size_t)nblk * bd * 8;
     return bytes ? bytes : 64;
 }
 // the fields of a store of `cap` slots that starts at b
 static void nk_point_fields(NkDev &d, double *b, int64_t cap, bool with_pid, bool with_nts) {
-    const int64_t nblk = (cap + 63) / 64;
     const int nf = 4 + (with_nts ? 1 : 0) + (with_pid ? 1 : 0);
     const int bd = nf * 64 + 32;
-    if (nk_layout_soa()) {
-        const int64_t n = nblk * 64;
-        int k = 4;
-        d.x = {b, 64}; d.y = {b + n, 64}; d.z = {b + 2 * n, 64}; d.occ = {b + 3 * n, 64};
-        d.nts = {with_nts ? b + (k++) * n : nullptr, 64};
-        d.pid = {with_pid ? (uint64_t *)(b + (k++) * n) : nullptr, 64};
-        d.w0 = {(uint32_t *)(b + k * n), 64};
-    } else {
-        int k = 4;
-        d.x = {b, bd}; d.y = {b + 64, bd}; d.z = {b + 128, bd}; d.occ = {b + 192, bd};
-        d.nts = {with_nts ? b + 64 * (k++) : nullptr, bd};
-        d.pid = {with_pid ? (uint64_t *)(b + 64 * (k++)) : nullptr, bd};
-        d.w0 = {(uint32_t *)(b + 64 * k), 2 * bd};
-    }
+    int k = 4;
+    d.x = {b, bd}; d.y = {b + 64, bd}; d.z = {b + 128, bd}; d.occ = {b + 192, bd};
+    d.nts = {with_nts ? b + 64 * (k++) : nullptr, bd};
+    d.pid = {with_pid ? (uint64_t *)(b + 64 * (k++)) : nullptr, bd};
+    d.w0 = {(uint32_t *)(b + 64 * k), 2 * bd};
 }
 static int nk_alloc_fields(nk_ctx *ctx, NkDev &d, int64_t cap, bool with_pid, bool with_nts) {
     const size_t bytes = nk_store_bytes(cap, with_pid, with_nts);
@@ -427,7 +421,6 @@ int nk_create(nk_ctx **out, int device_id, uint64_t seed) {
 }
 
 static void nk_specular_free(nk_ctx *ctx);
-static inline void nk_specular_free_fwd(nk_ctx *ctx) { nk_specular_free(ctx); }
 
 void nk_destroy(nk_ctx *ctx) {
     if (!ctx) return;
@@ -435,12 +428,11 @@ void nk_destroy(nk_ctx *ctx) {
     hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->rccl.CommDestroy) ctx->rccl.CommDestroy(ctx->comm);
     for (auto &e : ctx->evpool) hipEventDestroy(e);
-    nk_specular_free_fwd(ctx);
+    nk_specular_free(ctx);
     for (void *p : ctx->allocs) hipFree(p);
     for (void *p : ctx->pallocs) hipFree(p);
     if (ctx->acc) hipFree(ctx->acc);
     if (ctx->rbar) hipFree(ctx->rbar);
-    if (ctx->pin) hipHostFree(ctx->pin);
     if (ctx->hist) hipHostFree(ctx->hist);
     if (ctx->modetab_p) hipFree(ctx->modetab_p);
     if (ctx->m2s_dev) hipFree(ctx->m2s_dev);
@@ -899,7 +891,7 @@ int nk_set_mesh(nk_ctx *ctx, const nk_mesh *m) {
 // The box store is used when the mesh allows it, the tables sit in LDS, and nothing in this context spoke against it
 // (NK_NO_BOX=1: developer switch / tests of the cached layout on boxes).
 static inline bool nk_want_box(const nk_ctx *ctx) {
-    return ctx->have_mesh && ctx->mesh_box && !ctx->box_forbidden && !getenv("NK_NO_BOX") && !getenv("NK_SPLIT") && !nk_layout_soa() &&
+    return ctx->have_mesh && ctx->mesh_box && !ctx->box_forbidden && !getenv("NK_NO_BOX") && !getenv("NK_SPLIT") &&
            ctx->d.F <= NK_LDS_FACES && ctx->d.Fc <= NK_LDS_FACES;
 }
 
@@ -1022,7 +1014,7 @@ int nk_set_reservoirs(nk_ctx *ctx, const nk_reservoirs *r) {
     NK_ARG(r->R >= 0 && r->R <= 64, "nk_set_reservoirs: R must be in [0, 64]");
     NK_HIP(hipSetDevice(ctx->device));
     NkDev &d = ctx->d;
-    { int rc0 = nk_entry_tables_drop(ctx, false); if (rc0) return rc0; }
+    NK_TRY(nk_entry_tables_drop(ctx, false));
     d.R = r->R; d.res_gen = r->gen;
     d.res_nf = 0; d.res_lds = 0;
     NK_ARG((int64_t)d.R * d.M < (1ll << 28), "nk_set_reservoirs: R*Q*J too large for the particle id layout");
@@ -1166,13 +1158,12 @@ static int nk_normalize(nk_ctx *ctx, int honor_halt = 0) {
 static int nk_gather_live(nk_ctx *ctx, NkHostParticles &h, bool want_all) {
     NkDev &d = ctx->d;
     if (d.cap == 0) return NK_OK;
-    { int rcn_ = nk_normalize(ctx); if (rcn_) return rcn_; }
+    NK_TRY(nk_normalize(ctx));
     NK_HIP(hipStreamSynchronize(ctx->stream));
     std::vector<int32_t> cnt((size_t)d.nseg);
     NK_HIP(hipMemcpy(cnt.data(), d.seg_count, (size_t)d.nseg * 4, hipMemcpyDeviceToHost));
     int64_t live = 0;
     for (int c : cnt) live += c;
-    ctx->h_seg_count = cnt;
     if (!want_all) { h.x.resize((size_t)live); return NK_OK; }
     std::vector<double> bd;
     std::vector<uint32_t> bw;
@@ -1293,7 +1284,6 @@ static int nk_scatter(nk_ctx *ctx, int64_t N, const double *x, const double *y, 
     NK_HIP(hipMemcpy(d.seg_count, cnt.data(), (size_t)d.nseg * 4, hipMemcpyHostToDevice));
     if (d.seg_lo) NK_HIP(hipMemset(d.seg_lo, 0, (size_t)d.nseg * 4));      // (the particles were dealt from slot 0 of their segments)
     ctx->walked = false;
-    ctx->h_seg_count = cnt;
     return NK_OK;
 }
 
@@ -1547,11 +1537,34 @@ static inline int64_t nk_tiled_count(int64_t u, int64_t nu, int64_t pid_lo, int6
     const int64_t first = pid_lo % nu;
     return N / nu + (((u - first + nu) % nu) < N % nu ? 1 : 0);
 }
+// The arrays of a store of d.nseg segments and d.cap slots, for nk_alloc_particles and nk_regrow alike: the particle fields, the
+// segments' counters, the split sweep's event queues and (developer build) the stamp words.  Whatever it allocated before an
+// error is in ctx->pallocs, where the caller finds it.
+static int nk_alloc_store(nk_ctx *ctx, bool pid, bool nts, bool seg_lo, bool split) {
+    NkDev &d = ctx->d;
+    const size_t nseg = (size_t)d.nseg, cap = (size_t)d.cap;
+    NK_TRY(nk_alloc_fields(ctx, d, d.cap, pid, nts));
+    NK_TRY(nk_palloc(ctx, d.seg_count, nseg));
+    NK_TRY(nk_palloc(ctx, d.seg_new, nseg));
+    NK_TRY(nk_palloc(ctx, d.seg_bound, nseg));
+    if (seg_lo) NK_TRY(nk_palloc(ctx, d.seg_lo, nseg));
+    if (split) {
+        NK_TRY(nk_palloc(ctx, d.qx, cap)); NK_TRY(nk_palloc(ctx, d.qy, cap)); NK_TRY(nk_palloc(ctx, d.qz, cap));
+        NK_TRY(nk_palloc(ctx, d.qocc, cap)); NK_TRY(nk_palloc(ctx, d.qnts, cap));
+        NK_TRY(nk_palloc(ctx, d.qw0, cap));
+        if (pid) NK_TRY(nk_palloc(ctx, d.qpid, cap));
+        NK_TRY(nk_palloc(ctx, d.seg_evq, 2 * nseg + 1));
+    }
+#ifdef NK_STAMPS
+    NK_TRY(nk_palloc(ctx, d.stamps, nseg * 16));
+#endif
+    return NK_OK;
+}
 static int nk_alloc_particles(nk_ctx *ctx, int64_t capacity, const int32_t *mode = nullptr, int64_t N = 0,
                               const int32_t *umodes = nullptr, int64_t nu = 0, int64_t pid_lo = 0) {
     if (ctx) ctx->emitted_for = -1;
     NkDev &d = ctx->d;
-    { int rc0 = nk_entry_tables_drop(ctx, true); if (rc0) return rc0; }
+    NK_TRY(nk_entry_tables_drop(ctx, true));
     for (void *p : ctx->pallocs) hipFree(p);
     ctx->pallocs.clear();
     // Segments = load-balance granularity of the persistent sweep.  For large ensembles exactly ONE segment per resident wave
@@ -1587,7 +1600,7 @@ static int nk_alloc_particles(nk_ctx *ctx, int64_t capacity, const int32_t *mode
         if (same) break;
     }
     NK_ARG(d.nlmax < (1 << 14), "too many modes per segment for k_emit's packed entry word: use more particles (segments) or fewer modes");
-    { int rcm = nk_build_mode_map(ctx); if (rcm) return rcm; }
+    NK_TRY(nk_build_mode_map(ctx));
     {   // bits of the stored mode index; the rest of the 32-bit word holds facet + 1
         const int64_t maxidx = d.part ? d.nlmax - 1 : (d.M > 0 ? d.M - 1 : 0);
         int lb = 1;
@@ -1612,37 +1625,19 @@ static int nk_alloc_particles(nk_ctx *ctx, int64_t capacity, const int32_t *mode
     d.segcap = (int32_t)segcap;
     d.cap = nseg * segcap;
     ctx->timing.slots = d.cap;
-    const double *pd; const uint32_t *pw; const int32_t *pi; const uint64_t *pu;
-#define NK_PALLOC(T, field, ptr, count)                                                                \
-    do { int rc_ = nk_upload<T>(ctx, nullptr, (size_t)(count), &ptr, true); if (rc_) return rc_; d.field = (T *)ptr; } while (0)
-    { int rcf = nk_alloc_fields(ctx, d, d.cap, nk_want_pid(ctx), !d.box); if (rcf) return rcf; }
-    NK_PALLOC(int32_t, seg_count, pi, d.nseg);
-    NK_PALLOC(int32_t, seg_new, pi, d.nseg);
-    NK_PALLOC(int32_t, seg_bound, pi, d.nseg);
     d.seg_lo = nullptr; d.down = 0; ctx->walked = false;
-    NK_PALLOC(int32_t, seg_lo, pi, d.nseg);                 // (zeroed: the particles start at slot 0 of their segments)
     d.qx = d.qy = d.qz = d.qocc = d.qnts = nullptr; d.qw0 = nullptr; d.qpid = nullptr; d.seg_evq = nullptr;
-    if (nk_want_split(ctx)) {
-        NK_PALLOC(double, qx, pd, d.cap); NK_PALLOC(double, qy, pd, d.cap); NK_PALLOC(double, qz, pd, d.cap);
-        NK_PALLOC(double, qocc, pd, d.cap); NK_PALLOC(double, qnts, pd, d.cap);
-        NK_PALLOC(uint32_t, qw0, pw, d.cap);
-        if (d.pid) NK_PALLOC(uint64_t, qpid, pu, d.cap);
-        NK_PALLOC(int32_t, seg_evq, pi, 2 * (size_t)d.nseg + 1);
-    }
-#ifdef NK_STAMPS
-    { const unsigned long long *ps; int rc_ = nk_upload<unsigned long long>(ctx, nullptr, (size_t)d.nseg * 16, &ps, true); if (rc_) return rc_; d.stamps = (unsigned long long *)ps; }
-#endif
-#undef NK_PALLOC
+    NK_TRY(nk_alloc_store(ctx, nk_want_pid(ctx), !d.box, true, nk_want_split(ctx)));   // (seg_lo zeroed: the particles start at slot 0 of their segments)
     ctx->layout_key = (d.part ? 1 : 0) | (d.pid ? 2 : 0) | (d.qx ? 4 : 0) | (d.box ? 8 : 0);
     // tables that follow the segmentation: permuted mode records, 'one_to_one' inboxes
-    if (ctx->have_material) { int rc = nk_update_tau_window(ctx, true); if (rc) return rc; }
+    if (ctx->have_material) NK_TRY(nk_update_tau_window(ctx, true));
     if (ctx->inbox) { hipFree(ctx->inbox); ctx->inbox = nullptr; }
     if (ctx->inbox_n) { hipFree(ctx->inbox_n); ctx->inbox_n = nullptr; }
     d.sp_inbox = nullptr; d.sp_inbox_n = nullptr; d.sp_icap = 0;
     if (ctx->mig_buf) { hipFree(ctx->mig_buf); ctx->mig_buf = nullptr; }
     if (ctx->mig_n) { hipFree(ctx->mig_n); ctx->mig_n = nullptr; }
     d.mig_buf = nullptr; d.mig_n = nullptr; d.mig_cap = 0;
-    { int rcp = nk_place_store(ctx); if (rcp) return rcp; }
+    NK_TRY(nk_place_store(ctx));
     return nk_entry_tables_build(ctx);
 }
 
@@ -1678,7 +1673,7 @@ static int nk_ensure_inbox(nk_ctx *ctx) {
 // Grow every segment to `segcap_new` slots on the device (same segmentation: the particles keep their segments).
 static int nk_regrow(nk_ctx *ctx, int64_t segcap_new) {
     if (ctx) ctx->emitted_for = -1;
-    { int rcn_ = nk_normalize(ctx); if (rcn_) return rcn_; }
+    NK_TRY(nk_normalize(ctx));
     NkDev &d = ctx->d;
     NK_HIP(hipStreamSynchronize(ctx->stream));
     const NkDev old = d;
@@ -1689,23 +1684,8 @@ static int nk_regrow(nk_ctx *ctx, int64_t segcap_new) {
     NK_ARG((int64_t)old.nseg * segcap_new < (1ll << 31), "particle store too large for 32-bit slot arithmetic");
     d.segcap = (int32_t)segcap_new;
     d.cap = (int64_t)d.nseg * d.segcap;
-    const double *pd; const uint32_t *pw; const int32_t *pi; const uint64_t *pu;
-    int rc = NK_OK;
-#define NK_PALLOC(T, field, ptr, count)                                                                \
-    do { if (!rc) { rc = nk_upload<T>(ctx, nullptr, (size_t)(count), &ptr, true); if (!rc) d.field = (T *)ptr; } } while (0)
-    if (!rc) rc = nk_alloc_fields(ctx, d, d.cap, (bool)old.pid, (bool)old.nts);
-    NK_PALLOC(int32_t, seg_count, pi, d.nseg);
-    NK_PALLOC(int32_t, seg_new, pi, d.nseg);
-    NK_PALLOC(int32_t, seg_bound, pi, d.nseg);
-    if (old.seg_lo) NK_PALLOC(int32_t, seg_lo, pi, d.nseg);   // (the old store was moved down above; k_regrow copies from slot 0)
-    if (old.qx) {                                       // the event queues are empty between steps: new ones, nothing to copy
-        NK_PALLOC(double, qx, pd, d.cap); NK_PALLOC(double, qy, pd, d.cap); NK_PALLOC(double, qz, pd, d.cap);
-        NK_PALLOC(double, qocc, pd, d.cap); NK_PALLOC(double, qnts, pd, d.cap);
-        NK_PALLOC(uint32_t, qw0, pw, d.cap);
-        if (old.pid) NK_PALLOC(uint64_t, qpid, pu, d.cap);
-        NK_PALLOC(int32_t, seg_evq, pi, 2 * (size_t)d.nseg + 1);
-    }
-#undef NK_PALLOC
+    // (the old store was moved down above: k_regrow copies from slot 0; the event queues are empty between steps: new ones, nothing to copy)
+    const int rc = nk_alloc_store(ctx, (bool)old.pid, (bool)old.nts, old.seg_lo != nullptr, old.qx != nullptr);
     if (rc) {                                            // out of memory: keep the old store
         for (void *p : ctx->pallocs) hipFree(p);
         ctx->pallocs.swap(old_allocs);
@@ -1861,7 +1841,7 @@ int nk_init_boundaries(nk_ctx *ctx) {
 
 static int nk_flush_relax(nk_ctx *ctx, int honor_halt) {
     if (!ctx->pending_relax) return NK_OK;
-    { int rcn_ = nk_normalize(ctx); if (rcn_) return rcn_; }
+    NK_TRY(nk_normalize(ctx));
     k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(ctx->d, honor_halt);
     NK_HIP(hipGetLastError());
     ctx->pending_relax = false;
@@ -1935,7 +1915,7 @@ static int nk_field_refresh(nk_ctx *ctx) {
     // over the ranks -- a rank may have reserved on its own since the last call, which the others cannot know without asking:
     // one small all-reduce per nk_step call, the price of integers that can be all-reduced.
     double cap = (double)d.cap;
-    if (ctx->comm) { int rc = nk_comm_allreduce(ctx, &cap, 1); if (rc) return rc; }
+    if (ctx->comm) NK_TRY(nk_comm_allreduce(ctx, &cap, 1));
     const int64_t slots = std::max<int64_t>((int64_t)cap, F.cfg.capacity);      // (nk_field.capacity: a floor the caller chose)
     if (slots != F.capacity) nk_field_scale(F, slots);
     return NK_OK;
@@ -2025,7 +2005,7 @@ static int nk_modes_refresh(nk_ctx *ctx) {
     if (T_hi != Mo.T_hi) nk_modes_bound(Mo, d.kb, T_hi);
     // (with a communicator the scale must be the same on every rank: the slots are summed over the ranks, as for the field)
     double cap = (double)d.cap;
-    if (ctx->comm) { int rc = nk_comm_allreduce(ctx, &cap, 1); if (rc) return rc; }
+    if (ctx->comm) NK_TRY(nk_comm_allreduce(ctx, &cap, 1));
     const int64_t slots = std::max<int64_t>((int64_t)cap, Mo.cfg.capacity);
     if (slots != Mo.capacity) nk_modes_scale(Mo, slots);
     return NK_OK;
@@ -2064,197 +2044,290 @@ static void nk_modes_transpose(const TI *in, TO *out, int M, int S) {
 }
 }
 
-// Enqueue up to `nsteps` timesteps without host synchronisation, drain the stream, copy the history rows back.  A sweep that
-// sees a segment which COULD overflow at the following step raises the halt word; the remaining steps of the batch then do
-// nothing, *done < nsteps comes back, and nk_step grows the store (state intact, nothing dropped) and carries on.
-// The parts of a batch that are a context's own business, shared by nk_step_batch and the grouped batch of a replica group
-// (nk_group_batch), so that a member of a group keeps exactly the state a solo run keeps.
+// ================================================================================ a batch of steps
+// Up to `nsteps` timesteps are enqueued without host synchronisation, the stream is drained once, and the history rows are read.
+// A sweep that sees a segment which COULD overflow at the following step raises the halt word; the remaining steps of the batch
+// then do nothing, *done < nsteps comes back, and nk_step grows the store (state intact, nothing dropped) and carries on.
+// Three paths step a batch: nk_step_batch (launches per step), nk_step_resident (many steps per launch) and nk_group_batch (shared
+// launches of a replica group).  What a context keeps across them -- the frame NkBatch, the per-step record, the prelude of a
+// contains-check step, the read-back and the hand-over to the next call -- exists once, below; a path supplies only its launches.
+static inline NkRow nk_row(const nk_ctx *ctx) { return NkRow{ctx->d.NB, ctx->d.S}; }
+// the step tallies every `every`-th step (steps count from 1 there) / runs the contains check ahead of it (every contains_every-th)
+static inline bool nk_nth_step(int every, int64_t stepno) { return every > 0 && ((stepno + 1) % every) == 0; }
+static inline bool nk_flux_step(const nk_ctx *ctx, int64_t stepno) { return nk_nth_step(ctx->params.flux_every, stepno); }
+static inline bool nk_contains_step(const nk_ctx *ctx, int64_t stepno) {
+    return ctx->params.contains_every > 0 && (stepno % ctx->params.contains_every) == 0 && ctx->d.nS > 0;
+}
+
 // The history rows live in pinned HOST memory that the device writes directly (1.1 KB per step over PCIe by the one
 // workgroup of the update): no copy back, no fill kernel -- a driver that steps one by one pays for every operation of a
 // call (round 3: fill + two copies = a tenth of such a call).
 static int nk_batch_hist(nk_ctx *ctx, int32_t nsteps) {
-    const int HROW = ctx->d.NB + 2 * ctx->d.S + 8;
+    const size_t row_bytes = (size_t)nk_row(ctx).width() * sizeof(double);
     if (nsteps > ctx->hist_cap) {
         if (ctx->hist) hipHostFree(ctx->hist);
         ctx->hist = nullptr;
         ctx->hist_cap = 0;
         const int rows_alloc = nsteps < 1024 ? 1024 : nsteps;   // generous: a later, longer call must not pay a realloc
-        NK_HIP(hipHostMalloc((void **)&ctx->hist, (size_t)rows_alloc * HROW * sizeof(double), hipHostMallocMapped));
+        NK_HIP(hipHostMalloc((void **)&ctx->hist, (size_t)rows_alloc * row_bytes, hipHostMallocMapped));
         ctx->hist_cap = rows_alloc;
     }
     ctx->timing.batches += 1;
-    memset(ctx->hist, 0, (size_t)nsteps * HROW * sizeof(double));   // row_valid = 0 (host memory; the stream is idle between calls)
+    memset(ctx->hist, 0, (size_t)nsteps * row_bytes);   // row_valid = 0 (host memory; the stream is idle between calls)
     return NK_OK;
 }
-// What runs ahead of a contains_check step (every contains_every-th; nothing on the others): the segments moved down, the deferred
-// relaxation flushed (`pending` cleared, `flushed` set), k_contains.  *launches counts the kernels enqueued.
-static int nk_batch_prelude(nk_ctx *ctx, int64_t stepno, bool &pending, bool &flushed, int64_t *launches) {
+
+// The frame of a batch: what is decided once when it begins and what it hands over when it ends.
+struct NkBatch {
+    int g_sweep = 0, g_emit = 0;   // grids of the sweep and of the emission (k_emit, k_deliver, the emission's share of k_tail)
+    bool tail_emit = false;        // the next step's emission rides in this step's tail launch
+    bool alt = false;              // the sweeps alternate between walking their segments upwards and downwards
+    bool relax0 = false;           // the step before the batch left its relaxation deferred ...
+    bool flushed0 = false;         // ... and a k_relax ahead of the batch's first step has flushed it
+    bool emitted_ahead = false;    // the coming step's emission has run already (in the tail of the step before it)
+};
+// Is a relaxation deferred when step s of the batch begins?  Every step leaves its own deferred, so only the first step asks.
+// (This is the `pending` flag the three paths used to carry along: it has no state of its own.)
+static inline bool nk_batch_pending(const NkBatch &b, int s) { return s > 0 || b.relax0; }
+
+// Begin a batch.  resident: no tail launch, no alternating walk (k_resident emits inside and walks upwards only).
+// *launches counts the kernels enqueued.
+static int nk_batch_enter(nk_ctx *ctx, int32_t nsteps, NkBatch &b, bool resident = false, int64_t *launches = nullptr) {
     NkDev &d = ctx->d;
-    if (!(ctx->params.contains_every > 0 && (stepno % ctx->params.contains_every) == 0 && d.nS > 0)) return NK_OK;
-    const bool anchors = ctx->walked && d.seg_lo;
-    { int rcn_ = nk_normalize(ctx, 1); if (rcn_) return rcn_; }       // (k_relax, k_contains: particles from slot 0)
-    int64_t n = anchors ? 1 : 0;
-    if (pending) {
+    NK_TRY(nk_batch_hist(ctx, nsteps));
+    (void)nk_sweep_blocks(ctx);
+    b.g_sweep = std::min(ctx->g_sweep, (d.nseg + 3) / 4);
+    b.g_emit = std::min(ctx->num_cu * 8, (d.nseg + 3) / 4);
+    d.tree_lds_fam0 = d.tree_nfam; d.tree_lds_off = 0;         // (the split sweep may move the top of the face tree: nk_events_lds)
+    b.relax0 = ctx->pending_relax;
+    b.flushed0 = false;
+    // The next step's emission rides in the same launch as this step's reduce / update (k_tail) wherever it depends on neither
+    // (no rough facets, not 'one_to_one').  (On a second stream instead, the two cross-stream event waits per step cost more
+    // than the 12 us they hid: 0.289 against 0.270 ms per step on config 2, profiles/r03_notes.txt (11).)
+    b.tail_emit = !resident && d.R > 0 && d.res_gen != 2 && !getenv("NK_NO_TAIL_EMIT");
+    b.emitted_ahead = b.tail_emit && ctx->emitted_for == ctx->step;   // in the previous step's k_tail (maybe of the call before)
+    ctx->emitted_for = -1;
+    ctx->timing.emit_fused = resident ? 2 : b.tail_emit ? 1 : 0;      // (2: emission inside the resident kernel)
+    // the fused sweeps of small meshes (box store or cached store) alternate between walking their segments upwards and downwards
+    // (NkDev::down; nk_device.h), on every rank alike (the direction follows the step's parity).  Not the split sweep of large meshes:
+    // measured no gain there (config 4's store is ten times the memory-side cache).  NK_NO_ALTERNATE=1: never.
+    b.alt = !resident && d.seg_lo && nk_geom_mode(ctx) == 1 && !d.qx && !getenv("NK_NO_ALTERNATE");
+    if (!b.alt) {
+        if (launches && ctx->walked && d.seg_lo) *launches += 1;
+        NK_TRY(nk_normalize(ctx));
+    }
+    d.down = 0;
+    return NK_OK;
+}
+// What runs ahead of step s when it is a contains-check step (nothing on the others): the segments moved down, the deferred
+// relaxation flushed, k_contains.  *launches counts the kernels enqueued.
+static int nk_batch_prelude(nk_ctx *ctx, NkBatch &b, int s, int64_t *launches = nullptr) {
+    NkDev &d = ctx->d;
+    const int64_t stepno = ctx->step + s;
+    if (!nk_contains_step(ctx, stepno)) return NK_OK;
+    int64_t n = (ctx->walked && d.seg_lo) ? 1 : 0;
+    NK_TRY(nk_normalize(ctx, 1));       // (k_relax, k_contains: particles from slot 0)
+    if (nk_batch_pending(b, s)) {
         k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 1);
-        pending = false;
-        flushed = true;
+        if (s == 0) b.flushed0 = true;
         n += 1;
     }
     NK_GEOM_LAUNCH(k_contains, nk_sweep_grid(ctx), nk_lds(ctx, true), d, (uint32_t)stepno);
     if (launches) *launches += n + 1;
     return NK_OK;
 }
+// What the launches of step s are passed (NkGroupRec, nk_group.h: a group uploads these, the other paths pass the values).
+static NkGroupRec nk_batch_rec(const nk_ctx *ctx, const NkBatch &b, int s) {
+    const int64_t stepno = ctx->step + s;
+    NkGroupRec rec;
+    rec.step = (uint32_t)stepno;
+    rec.do_relax = (nk_batch_pending(b, s) && !nk_contains_step(ctx, stepno)) ? 1 : 0;   // (there k_relax has run ahead: nk_batch_prelude)
+    rec.do_flux = nk_flux_step(ctx, stepno) ? 1 : 0;
+    rec.down = b.alt ? (int32_t)(stepno & 1) : 0;
+    rec.hist_row = ctx->hist + (size_t)s * nk_row(ctx).width();
+    rec.acc = ctx->acc;
+    return rec;
+}
 // After the wait: the rows into h, the steps that ran, and the halt words as the last step that ran left them (its update wrote
 // them behind the row); no row: ask the device.
 static int nk_batch_collect(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
-    const NkDev &d = ctx->d;
-    const int S = d.S, NB = d.NB, HROW = NB + 2 * S + 8;
-    h.resize((size_t)nsteps * HROW);
-    memcpy(h.data(), ctx->hist, (size_t)nsteps * HROW * sizeof(double));
+    const NkRow row = nk_row(ctx);
+    const size_t W = (size_t)row.width();
+    h.resize((size_t)nsteps * W);
+    memcpy(h.data(), ctx->hist, (size_t)nsteps * W * sizeof(double));
     int32_t nd = 0;
-    while (nd < nsteps && h[(size_t)nd * HROW + NB + 2 * S + 1] != 0.0) ++nd;
-    if (nd > 0) for (int k_ = 0; k_ < 4; ++k_) ctx->halt_words[k_] = (int32_t)h[(size_t)(nd - 1) * HROW + NB + 2 * S + 4 + k_];
-    else NK_HIP(hipMemcpy(ctx->halt_words, d.halt, 16, hipMemcpyDeviceToHost));
+    while (nd < nsteps && h[(size_t)nd * W + row.valid()] != 0.0) ++nd;
+    if (nd > 0) for (int k_ = 0; k_ < 4; ++k_) ctx->halt_words[k_] = (int32_t)h[(size_t)(nd - 1) * W + row.halt(k_)];
+    else NK_HIP(hipMemcpy(ctx->halt_words, ctx->d.halt, 16, hipMemcpyDeviceToHost));
     *done = nd;
     return NK_OK;
 }
 // How a batch of which nd steps ran leaves the emission that ran ahead and the deferred relaxation.
-static void nk_batch_leave(nk_ctx *ctx, int32_t nsteps, int32_t nd, bool tail_emit, bool relax0, bool flushed_first) {
+static void nk_batch_leave(nk_ctx *ctx, const NkBatch &b, int32_t nsteps, int32_t nd) {
     // the emission that ran ahead in the last tail is good for the next call unless the batch halted (the store grows first)
     const int32_t *hw_ = ctx->halt_words;
-    ctx->emitted_for = (tail_emit && nd == nsteps && !hw_[0] && !hw_[2] && !hw_[3]) ? ctx->step + nsteps : -1;
+    ctx->emitted_for = (b.tail_emit && nd == nsteps && !hw_[0] && !hw_[2] && !hw_[3]) ? ctx->step + nsteps : -1;
     // the deferred relaxation as the device left it: pending after any completed step; if none ran, whatever it was before,
     // unless a k_relax ahead of the first step flushed it (that kernel honours the halt word, which was clear then)
     if (nd > 0) ctx->pending_relax = true;
-    else ctx->pending_relax = relax0 && !flushed_first;
+    else ctx->pending_relax = b.relax0 && !b.flushed0;
+}
+// the two timing events of a call (evpool[64], [65]) and four per timed step; created once and reused
+static int nk_batch_events(nk_ctx *ctx) {
+    if (!ctx->evpool.empty()) return NK_OK;
+    ctx->evpool.resize(16 * 4 + 2);
+    for (auto &e : ctx->evpool) NK_HIP(hipEventCreate(&e));
+    return NK_OK;
 }
 
+// k_events keeps the top of the face tree in LDS: as many whole levels as fit beside its tables at NK_EVENTS_OCC workgroups per CU
+// (160 KB per CU; NK_EVENTS_TREE_LDS = bytes to use at most, 0 = none: developer probe).  Returns the kernel's dynamic LDS and
+// sets NkDev::tree_lds_fam0 / tree_lds_off.
+static size_t nk_events_lds(nk_ctx *ctx, size_t lds_g) {
+    NkDev &d = ctx->d;
+    size_t lds_ev = lds_g;
+    if (!(d.qx && nk_geom_mode(ctx) == 2 && d.NG > 0 && d.tree_nfam > 0)) return lds_ev;
+    const size_t off = (lds_g + 15) & ~(size_t)15, fixed = off + (size_t)NK_EVENTS_PEND * NK_EV_WG * 4 + 1024;
+    size_t budget = (size_t)160 * 1024 / NK_EV_PER_CU > fixed ? (size_t)160 * 1024 / NK_EV_PER_CU - fixed : 0;
+    if (const char *e = getenv("NK_EVENTS_TREE_LDS")) { const size_t v = (size_t)atol(e); if (v < budget) budget = v; }
+    for (int l = 0; l <= d.tree_top; ++l) {
+        const int fam0 = d.tree_base[l] >> 2;
+        const size_t bytes = (size_t)(d.tree_nfam - fam0) * NK_TREE_FAMILY_FLOATS * 4;
+        if (bytes <= budget) { d.tree_lds_fam0 = fam0; d.tree_lds_off = (int32_t)off; lds_ev = off + bytes; break; }
+    }
+    if (getenv("NK_VERBOSE") && ctx->timing.batches <= 1)
+        fprintf(stderr, "[nanokappa_hip] k_events: families %d .. %d of the face tree in LDS (%zu B of %zu B per workgroup)\n", d.tree_lds_fam0, d.tree_nfam, lds_ev - off, lds_ev);
+    return lds_ev;
+}
+// The side tallies of the particles the sweep of batch step s has just tallied (before the tail: T_sv still the tally's; timed
+// with the tail, nk_timing.events_kernel_ms).  band_s: the batch step of each band row so far.
+static int nk_side_tallies(nk_ctx *ctx, int s, std::vector<int> &band_s) {
+    const int64_t stepno = ctx->step + s;
+    if (!nk_flux_step(ctx, stepno)) return NK_OK;
+    const int nranks = ctx->comm ? ctx->comm_nranks : 1;
+    // the band-resolved flux: one row per heat-flux step (k_spectral)
+    if (ctx->band_B > 0) {
+        NK_TRY(nk_band_pass(ctx, false, ctx->band_rows_d + band_s.size() * 4 * (size_t)ctx->d.S * ctx->band_B));
+        band_s.push_back(s);
+    }
+    // the field of the same particles on field steps (k_field; one launch per field step whatever the grid size)
+    if (ctx->field.on && nk_nth_step(ctx->field.cfg.every, stepno)) {
+        NK_TRY(nk_field_sample(ctx, false, false));
+        NK_HIP(nk_field_accumulate(ctx->field.g, ctx->field, nranks, ctx->stream));
+        // ... and the same sums per (cell, group of modes): taken or dropped with the field's sample
+        if (ctx->fgroups.on) {
+            NK_TRY(nk_field_sample(ctx, true, false));
+            NK_HIP(nk_field_accumulate(ctx->fgroups.g, ctx->field, nranks, ctx->stream));
+        }
+    }
+    // the mode-resolved tally of the same particles on mode steps (k_modes: one wave per segment)
+    if (ctx->modes.on && nk_nth_step(ctx->modes.cfg.every, stepno)) {
+        NK_TRY(nk_modes_sample(ctx, false));
+        NK_HIP(nk_modes_accumulate(ctx->modes, nranks, ctx->num_cu, ctx->stream));
+    }
+    return NK_OK;
+}
+// The band rows of the nd steps that ran, from the device to ctx->band_rows / band_steps.
+static int nk_band_collect(nk_ctx *ctx, const std::vector<int> &band_s, int32_t nd) {
+    if (band_s.empty()) return NK_OK;
+    const size_t rl = 4 * (size_t)ctx->d.S * ctx->band_B;
+    std::vector<double> br(band_s.size() * rl);
+    NK_HIP(hipMemcpyAsync(br.data(), ctx->band_rows_d, br.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    // a step whose migrants did not all fit their segments (k_deliver: halt word 2, the store grows before they are
+    // delivered) has tallied particles the pass could not see: no row for it
+    const int unseen = ctx->halt_words[2] ? nd - 1 : -1;
+    for (size_t r = 0; r < band_s.size(); ++r) {
+        if (band_s[r] >= nd || band_s[r] == unseen) continue;
+        ctx->band_rows.insert(ctx->band_rows.end(), br.begin() + r * rl, br.begin() + (r + 1) * rl);
+        ctx->band_steps.push_back(ctx->step + band_s[r]);
+    }
+    return NK_OK;
+}
+// nk_timing of a batch of nsteps of which nd ran: the kernels of its first nev steps (events ev[4 s .. 4 s + 3]) and the whole call
+static int nk_batch_timing(nk_ctx *ctx, int nev, int32_t nsteps, int32_t nd) {
+    const hipEvent_t *ev = ctx->evpool.data();
+    float ms = 0.f;
+    double sk = 0.0, ek = 0.0, vk = 0.0;
+    const int nt = nd < nev ? nd : nev;
+    for (int s = 0; s < nt; ++s) {
+        NK_HIP(hipEventElapsedTime(&ms, ev[4 * s], ev[4 * s + 1])); ek += ms;
+        NK_HIP(hipEventElapsedTime(&ms, ev[4 * s + 1], ev[4 * s + 2])); sk += ms;
+        NK_HIP(hipEventElapsedTime(&ms, ev[4 * s + 2], ev[4 * s + 3])); vk += ms;
+    }
+    NK_HIP(hipEventElapsedTime(&ms, ev[64], ev[65]));
+    if (nt > 0 && nd == nsteps) {
+        ctx->timing.step_kernel_ms = sk / nt;
+        ctx->timing.emit_kernel_ms = ek / nt;
+        ctx->timing.events_kernel_ms = vk / nt;
+        ctx->timing.total_ms = ms;
+    }
+    return NK_OK;
+}
+#ifdef NK_STAMPS
+#include "nk_stamps.h"
+#endif
+
+// The launch-per-step path: the sequence of a step, written once.
 static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
     NkDev &d = ctx->d;
-    const int S = d.S, R = d.R, NB = d.NB;
-    const int HROW = NB + 2 * S + 8;
-    { int rch_ = nk_batch_hist(ctx, nsteps); if (rch_) return rch_; }
+    const int R = d.R, NB = d.NB;
+    NkBatch b;
+    NK_TRY(nk_batch_enter(ctx, nsteps, b));
     const size_t lds_g = nk_lds(ctx, true), lds_w = nk_lds(ctx, true, d.pid ? 3 : 2), lds_e = nk_lds(ctx, true, 1);
+    const size_t lds_t = lds_e > (size_t)(NK_WG * 8 + 16) ? lds_e : (size_t)(NK_WG * 8 + 16);
+    const size_t lds_ev = nk_events_lds(ctx, lds_g);
     const int gm_ = nk_geom_mode(ctx);
     const bool rough_ = d.Fr > 0, rbf_ = d.sv_interp == 3, pid_ = (bool)d.pid, split_ = d.qx != nullptr;
     const bool lrec_ = nk_want_lrec(ctx);
-    (void)nk_sweep_blocks(ctx);
-    const int g_sweep = ctx->g_sweep < (d.nseg + 3) / 4 ? ctx->g_sweep : (d.nseg + 3) / 4;
-    const int g_emit = ctx->num_cu * 8 < (d.nseg + 3) / 4 ? ctx->num_cu * 8 : (d.nseg + 3) / 4;
+    const int g_sweep = b.g_sweep, g_emit = b.g_emit;
     const int g_ev = split_ ? ctx->num_cu * NK_EV_PER_CU : 0;    // k_events: resident waves drawing from all queues
-    // k_events keeps the top of the face tree in LDS: as many whole levels as fit beside its tables at NK_EVENTS_OCC workgroups per CU
-    // (160 KB per CU; NK_EVENTS_TREE_LDS = bytes to use at most, 0 = none: developer probe)
-    size_t lds_ev = lds_g;
-    d.tree_lds_fam0 = d.tree_nfam; d.tree_lds_off = 0;
-    if (split_ && gm_ == 2 && d.NG > 0 && d.tree_nfam > 0) {
-        const size_t off = (lds_g + 15) & ~(size_t)15, fixed = off + (size_t)NK_EVENTS_PEND * NK_EV_WG * 4 + 1024;
-        size_t budget = (size_t)160 * 1024 / NK_EV_PER_CU > fixed ? (size_t)160 * 1024 / NK_EV_PER_CU - fixed : 0;
-        if (const char *e = getenv("NK_EVENTS_TREE_LDS")) { const size_t v = (size_t)atol(e); if (v < budget) budget = v; }
-        for (int l = 0; l <= d.tree_top; ++l) {
-            const int fam0 = d.tree_base[l] >> 2;
-            const size_t bytes = (size_t)(d.tree_nfam - fam0) * NK_TREE_FAMILY_FLOATS * 4;
-            if (bytes <= budget) { d.tree_lds_fam0 = fam0; d.tree_lds_off = (int32_t)off; lds_ev = off + bytes; break; }
-        }
-        if (getenv("NK_VERBOSE") && ctx->timing.batches <= 1)
-            fprintf(stderr, "[nanokappa_hip] k_events: families %d .. %d of the face tree in LDS (%zu B of %zu B per workgroup)\n", d.tree_lds_fam0, d.tree_nfam, lds_ev - off, lds_ev);
-    }
     const int rows = g_sweep + g_ev;
     // per-kernel timing on the first 4 steps of a batch; none for the short calls of a driver that steps one by one (six event
     // records are a tenth of such a call).  Every record is a marker packet between two dependent kernels: measured ~2 us each
     // on the stream -- with records on 16 of a region's 20 steps (round 3) a step took 0.213 ms, in 100-step batches 0.206.
     const int nev = nsteps < 4 ? 0 : 4;
-    if (ctx->evpool.empty()) {                           // events are created once and reused
-        ctx->evpool.resize(16 * 4 + 2);
-        for (auto &e : ctx->evpool) NK_HIP(hipEventCreate(&e));
-    }
+    NK_TRY(nk_batch_events(ctx));
     hipEvent_t *ev = ctx->evpool.data();
-    hipEvent_t t0 = ctx->evpool[64], t1 = ctx->evpool[65];
-    const bool relax0 = ctx->pending_relax;
-    NK_HIP(hipEventRecord(t0, ctx->stream));
-    bool pending = ctx->pending_relax;
-    std::vector<char> relax_flushed((size_t)nsteps, 0);       // steps whose deferred relaxation k_relax ran before them
-    // The next step's emission rides in the same launch as this step's reduce / update (k_tail) wherever it depends on neither
-    // (no rough facets, not 'one_to_one').  (On a second stream instead, the two cross-stream event waits per step cost more
-    // than the 12 us they hid: 0.289 against 0.270 ms per step on config 2, profiles/r03_notes.txt (11).)
-    const bool tail_emit = R > 0 && d.res_gen != 2 && !getenv("NK_NO_TAIL_EMIT");
-    const size_t lds_t = lds_e > (size_t)(NK_WG * 8 + 16) ? lds_e : (size_t)(NK_WG * 8 + 16);
-    bool emitted_ahead = tail_emit && ctx->emitted_for == ctx->step;   // this step's emission already ran in the previous step's k_tail (maybe of the call before)
-    ctx->emitted_for = -1;
-    ctx->timing.emit_fused = tail_emit ? 1 : 0;
-    // the fused sweeps of small meshes (box store or cached store) alternate between walking their segments upwards and downwards
-    // (NkDev::down; nk_device.h), on every rank alike (the direction follows the step's parity).  Not the split sweep of large meshes:
-    // measured no gain there (config 4's store is ten times the memory-side cache).  NK_NO_ALTERNATE=1: never.
-    const bool alt = d.seg_lo && gm_ == 1 && !split_ && !getenv("NK_NO_ALTERNATE");
-    if (!alt) { int rcn_ = nk_normalize(ctx); if (rcn_) return rcn_; }
-    d.down = 0;
-    // band-resolved heat flux: one row per heat-flux step of the batch (k_spectral after the sweep; nothing when off)
-    const bool bands_ = ctx->band_B > 0;
-    std::vector<int> band_s;                                  // batch step of each row
-    if (bands_) {
-        const int fe = ctx->params.flux_every;
+    NK_HIP(hipEventRecord(ev[64], ctx->stream));
+    std::vector<int> band_s;                                  // batch step of each band row (one per heat-flux step; none when off)
+    if (ctx->band_B > 0) {
         int nflux = 0;
-        for (int s = 0; s < nsteps; ++s) nflux += (fe > 0 && ((ctx->step + s + 1) % fe) == 0) ? 1 : 0;
-        if (nflux > 0) { int rcb_ = nk_band_ensure(ctx, nflux); if (rcb_) return rcb_; }
+        for (int s = 0; s < nsteps; ++s) nflux += nk_flux_step(ctx, ctx->step + s) ? 1 : 0;
+        if (nflux > 0) NK_TRY(nk_band_ensure(ctx, nflux));
     }
     for (int s = 0; s < nsteps; ++s) {
-        const int64_t stepno = ctx->step + s;
-        const uint32_t step = (uint32_t)stepno;
-        { bool fl_ = false; int rcp_ = nk_batch_prelude(ctx, stepno, pending, fl_, nullptr); if (rcp_) return rcp_; if (fl_) relax_flushed[(size_t)s] = 1; }
-        const int fe = ctx->params.flux_every;
-        const int do_flux = (fe > 0 && ((stepno + 1) % fe) == 0) ? 1 : 0;
+        NK_TRY(nk_batch_prelude(ctx, b, s));
+        const NkGroupRec rec = nk_batch_rec(ctx, b, s);
+        const uint32_t step = rec.step;
+        const int do_flux = rec.do_flux;
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s], ctx->stream));
         if (R > 0 && d.res_gen == 2) k_emit_one_to_one<<<ctx->num_cu * 4, NK_WG, 0, ctx->stream>>>(d, step);
-        if (R > 0 && !emitted_ahead) NK_EMIT_LAUNCH(k_emit, g_emit, lds_e, d, step);
+        if (R > 0 && !b.emitted_ahead) NK_EMIT_LAUNCH(k_emit, g_emit, lds_e, d, step);
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s + 1], ctx->stream));
-        {
-            const int rl = pending ? 1 : 0;
-            if (alt) { d.down = (int32_t)(stepno & 1); ctx->walked = true; }
-            NK_SWEEP_DISPATCH(gm_, rough_, rbf_, pid_, split_, lrec_, (KERNEL<<<g_sweep, NK_WG, lds_w, ctx->stream>>>(d, step, rl, do_flux)));
-            d.down = 0;
-            if (split_) {
-                k_events_begin<<<1, 1024, 0, ctx->stream>>>(d);
-                const int64_t ev_key = (int64_t)lds_ev * 64 + (gm_ | (rough_ << 2) | (rbf_ << 3) | (pid_ << 4));
-                if (ctx->ev_lds_set != ev_key) {        // more than the default 64 KB of dynamic LDS has to be asked for, per kernel
-                    hipError_t ea_ = hipSuccess;
-                    NK_EVENTS_DISPATCH(gm_, rough_, rbf_, pid_, (ea_ = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ev)));
-                    NK_HIP(ea_);
-                    ctx->ev_lds_set = ev_key;
-                }
-                NK_EVENTS_DISPATCH(gm_, rough_, rbf_, pid_, (KERNEL<<<g_ev, NK_EV_WG, lds_ev, ctx->stream>>>(d, step, do_flux, g_sweep)));
-                k_events_end<<<(d.nseg + 255) / 256, 256, 0, ctx->stream>>>(d);
+        if (b.alt) ctx->walked = true;
+        d.down = rec.down;
+        NK_SWEEP_DISPATCH(gm_, rough_, rbf_, pid_, split_, lrec_, (KERNEL<<<g_sweep, NK_WG, lds_w, ctx->stream>>>(d, step, rec.do_relax, do_flux)));
+        d.down = 0;
+        if (split_) {
+            k_events_begin<<<1, 1024, 0, ctx->stream>>>(d);
+            const int64_t ev_key = (int64_t)lds_ev * 64 + (gm_ | (rough_ << 2) | (rbf_ << 3) | (pid_ << 4));
+            if (ctx->ev_lds_set != ev_key) {        // more than the default 64 KB of dynamic LDS has to be asked for, per kernel
+                hipError_t ea_ = hipSuccess;
+                NK_EVENTS_DISPATCH(gm_, rough_, rbf_, pid_, (ea_ = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ev)));
+                NK_HIP(ea_);
+                ctx->ev_lds_set = ev_key;
             }
+            NK_EVENTS_DISPATCH(gm_, rough_, rbf_, pid_, (KERNEL<<<g_ev, NK_EV_WG, lds_ev, ctx->stream>>>(d, step, do_flux, g_sweep)));
+            k_events_end<<<(d.nseg + 255) / 256, 256, 0, ctx->stream>>>(d);
         }
         // rough facets: the migrants of this step go to their segments before the tallies are reduced (and before the next step's
         // emission, in the tail launch, appends behind them)
         if (d.mig_buf) k_deliver<<<g_emit, NK_WG, 0, ctx->stream>>>(d, 1);
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s + 2], ctx->stream));
-        // the band-resolved flux of the particles the sweep has just tallied (before the tail: T_sv still the tally's; timed
-        // with the tail, nk_timing.events_kernel_ms)
-        if (bands_ && do_flux) {
-            int rcb_ = nk_band_pass(ctx, false, ctx->band_rows_d + band_s.size() * 4 * (size_t)S * ctx->band_B);
-            if (rcb_) return rcb_;
-            band_s.push_back(s);
-        }
-        // the field of the same particles on field steps (k_field; one launch per field step whatever the grid size)
-        if (ctx->field.on && do_flux && ((stepno + 1) % ctx->field.cfg.every) == 0) {
-            int rcf_ = nk_field_sample(ctx, false, false);
-            if (rcf_) return rcf_;
-            NK_HIP(nk_field_accumulate(ctx->field.g, ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
-            // ... and the same sums per (cell, group of modes): taken or dropped with the field's sample
-            if (ctx->fgroups.on) {
-                int rcg_ = nk_field_sample(ctx, true, false);
-                if (rcg_) return rcg_;
-                NK_HIP(nk_field_accumulate(ctx->fgroups.g, ctx->field, ctx->comm ? ctx->comm_nranks : 1, ctx->stream));
-            }
-        }
-        // the mode-resolved tally of the same particles on mode steps (k_modes: one wave per segment)
-        if (ctx->modes.on && do_flux && ((stepno + 1) % ctx->modes.cfg.every) == 0) {
-            int rcm_ = nk_modes_sample(ctx, false);
-            if (rcm_) return rcm_;
-            NK_HIP(nk_modes_accumulate(ctx->modes, ctx->comm ? ctx->comm_nranks : 1, ctx->num_cu, ctx->stream));
-        }
-        double *hrow = ctx->hist + (size_t)s * HROW;
-        const bool ahead = tail_emit;                          // the next step's emission beside this step's tail (the last step's too: for the next call)
+        NK_TRY(nk_side_tallies(ctx, s, band_s));
+        double *hrow = rec.hist_row;
+        const bool ahead = b.tail_emit;                        // the next step's emission beside this step's tail (the last step's too: for the next call)
         if (ctx->comm) {
             if (ahead) NK_EMIT_LAUNCH(k_tail, NB + g_emit, lds_t, d, step + 1u, rows, ctx->acc, hrow, do_flux, 0, NB);
             else k_reduce<<<NB, NK_WG, 0, ctx->stream>>>(d, rows, ctx->acc, hrow, do_flux, 0);
@@ -2266,12 +2339,11 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
         } else {
             k_reduce<<<NB, NK_WG, 0, ctx->stream>>>(d, rows, ctx->acc, hrow, do_flux, 1);
         }
-        emitted_ahead = ahead;
+        b.emitted_ahead = ahead;
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s + 3], ctx->stream));
-        pending = true;
         if ((s & 63) == 0) NK_HIP(hipGetLastError());   // a bad launch configuration shows at the first step of a batch (every step launches the same)
     }
-    NK_HIP(hipEventRecord(t1, ctx->stream));
+    NK_HIP(hipEventRecord(ev[65], ctx->stream));
     NK_HIP(hipGetLastError());
     // the history rows and the halt words come back through pinned memory, enqueued behind the steps: ONE wait per call (a
     // Population.run_timestep is one such call per step -- the reference driver's granularity, nanokappa.py:91-98)
@@ -2279,138 +2351,13 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     // stream -- the wake-up of a blocked wait is a tenth of such a call
     if (nsteps <= 4) { hipError_t q_; while ((q_ = hipStreamQuery(ctx->stream)) == hipErrorNotReady) { } if (q_ != hipSuccess) { ctx->err = std::string("hipStreamQuery: ") + hipGetErrorString(q_); return NK_ERR_HIP; } }
     NK_HIP(hipStreamSynchronize(ctx->stream));
-    { int rcc_ = nk_batch_collect(ctx, nsteps, h, done); if (rcc_) return rcc_; }
+    NK_TRY(nk_batch_collect(ctx, nsteps, h, done));
 #ifdef NK_STAMPS
-    if (d.stamps) {                                     // developer build: section shares of the LAST sweep of the batch
-        std::vector<unsigned long long> st((size_t)d.nseg * 16);
-        NK_HIP(hipMemcpy(st.data(), d.stamps, st.size() * 8, hipMemcpyDeviceToHost));
-        double sum[7] = {0, 0, 0, 0, 0, 0, 0};
-        for (int sgm = 0; sgm < d.nseg; ++sgm) for (int k = 0; k < 7; ++k) sum[k] += (double)st[(size_t)sgm * 8 + k];
-        double tot = 0; for (int k = 0; k < 6; ++k) tot += sum[k];
-        {   // in-kernel shader clock of the sweep (s_memtime against the 100 MHz s_memrealtime, per segment; median)
-            std::vector<unsigned long long> clk;
-            for (int sgm = 0; sgm < d.nseg; ++sgm) clk.push_back(st[(size_t)sgm * 8 + 7]);
-            std::sort(clk.begin(), clk.end());
-            // wall-clock marks (10 ns ticks of the 100 MHz counter): where the launch's time goes outside the tile loops
-            unsigned long long e0 = ~0ull, x1 = 0;
-            std::vector<double> pro, loop, epi, fin;
-            for (int sgm = 0; sgm < d.nseg; ++sgm) {
-                const unsigned long long *w = &st[((size_t)d.nseg + sgm) * 8];
-                if (!w[0] || !w[3]) continue;
-                e0 = std::min(e0, w[0]); x1 = std::max(x1, w[3]);
-            }
-            for (int sgm = 0; sgm < d.nseg; ++sgm) {
-                const unsigned long long *w = &st[((size_t)d.nseg + sgm) * 8];
-                if (!w[0] || !w[3]) continue;
-                pro.push_back((double)(w[1] - w[0]) * 0.01); loop.push_back((double)(w[2] - w[1]) * 0.01);
-                epi.push_back((double)(w[3] - w[2]) * 0.01); fin.push_back((double)(w[3] - e0) * 0.01);
-            }
-            auto q = [](std::vector<double> v, const char *nm) {
-                if (v.empty()) return;
-                std::sort(v.begin(), v.end());
-                double sm = 0; for (double x : v) sm += x;
-                fprintf(stderr, "[stamps] %s [us]: min %.1f  p10 %.1f  median %.1f  mean %.1f  p90 %.1f  max %.1f\n", nm, v.front(), v[v.size() / 10], v[v.size() / 2], sm / v.size(), v[v.size() * 9 / 10], v.back());
-            };
-            {   // k_emit's marks of the same step (words 4-7 of the second row): entry, tables in LDS, first entries evaluated, done
-                unsigned long long m0 = ~0ull, m3 = 0;
-                std::vector<double> a, b, c, fin2;
-                for (int sgm = 0; sgm < d.nseg; ++sgm) { const unsigned long long *w = &st[((size_t)d.nseg + sgm) * 8 + 4]; if (w[0] && w[3]) { m0 = std::min(m0, w[0]); m3 = std::max(m3, w[3]); } }
-                for (int sgm = 0; sgm < d.nseg; ++sgm) {
-                    const unsigned long long *w = &st[((size_t)d.nseg + sgm) * 8 + 4];
-                    if (!w[0] || !w[3]) continue;
-                    a.push_back((double)(w[1] - w[0]) * 0.01); b.push_back((double)(w[2] - w[1]) * 0.01); c.push_back((double)(w[3] - w[2]) * 0.01);
-                    fin2.push_back((double)(w[3] - m0) * 0.01);
-                }
-                auto q2 = [](std::vector<double> v, const char *nm) {
-                    if (v.empty()) return;
-                    std::sort(v.begin(), v.end());
-                    double sm = 0; for (double x : v) sm += x;
-                    fprintf(stderr, "[stamps] k_emit %s [us]: min %.1f  median %.1f  mean %.1f  p90 %.1f  max %.1f\n", nm, v.front(), v[v.size() / 2], sm / v.size(), v[v.size() * 9 / 10], v.back());
-                };
-                if (!a.empty()) {
-                    fprintf(stderr, "[stamps] k_emit first entry -> last wave done: %.1f us\n", (double)(m3 - m0) * 0.01);
-                    q2(a, "entry -> tables in LDS"); q2(b, "-> first chunk of entries evaluated"); q2(c, "-> particles built and stored"); q2(fin2, "wave done, after the first entry");
-                }
-            }
-            fprintf(stderr, "[stamps] first entry -> last exit: %.1f us over %zu waves\n", (double)(x1 - e0) * 0.01, pro.size());
-            {   // where do the slow waves sit?  mean tile-loop time by workgroup index mod 8 (the XCD under round-robin placement),
-                // by wave within the workgroup, and by thirds of the grid
-                double xs[8] = {0}, xn[8] = {0}, ws[4] = {0}, wn[4] = {0}, gs[4] = {0}, gn[4] = {0}, rs[8] = {0}, rn[8] = {0};
-                for (int sgm = 0; sgm < d.nseg; ++sgm) {
-                    const unsigned long long *w = &st[((size_t)d.nseg + sgm) * 8];
-                    if (!w[0] || !w[3]) continue;
-                    const double t = (double)(w[2] - w[1]) * 0.01;
-                    const int wg = sgm / 4;
-                    xs[wg % 8] += t; xn[wg % 8] += 1; ws[sgm % 4] += t; wn[sgm % 4] += 1;
-                    const int third = (int)((int64_t)sgm * 4 / d.nseg); gs[third] += t; gn[third] += 1;
-                    const int rk = wg / ctx->num_cu; if (rk < 8) { rs[rk] += t; rn[rk] += 1; }
-                }
-                fprintf(stderr, "[stamps] tile loop mean [us] by workgroup %% 8:");
-                for (int k = 0; k < 8; ++k) fprintf(stderr, " %.1f", xn[k] ? xs[k] / xn[k] : 0.0);
-                fprintf(stderr, " | by wave of the workgroup:");
-                for (int k = 0; k < 4; ++k) fprintf(stderr, " %.1f", wn[k] ? ws[k] / wn[k] : 0.0);
-                fprintf(stderr, " | by quarter of the grid:");
-                for (int k = 0; k < 4; ++k) fprintf(stderr, " %.1f", gn[k] ? gs[k] / gn[k] : 0.0);
-                fprintf(stderr, " | by workgroup / CUs (the k-th workgroup of a CU under in-order dispatch):");
-                for (int k = 0; k < 8; ++k) if (rn[k]) fprintf(stderr, " %.1f", rs[k] / rn[k]);
-                fprintf(stderr, "\n");
-            }
-            q(pro, "entry -> tile loop (tables into LDS, records)"); q(loop, "tile loop"); q(epi, "tile loop end -> wave through (flush, workgroup barrier, tally row)");
-            q(fin, "wave through, after the first entry");
-            fprintf(stderr, "[stamps] shader clock inside k_sweep: median %.0f MHz (min %.0f, max %.0f)\n", clk[clk.size() / 2] / 10.0, clk.front() / 10.0, clk.back() / 10.0);
-        }
-        fprintf(stderr, "[stamps] cycles per tile: arrive %.0f  relax+drift %.0f  tally+store %.0f  pack/merge %.0f  event %.0f  event tally/store/repack %.0f  | total %.0f (tiles %.0f)\n",
-                sum[0] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6], sum[4] / sum[6], sum[5] / sum[6], tot / sum[6], sum[6]);
-        if (d.qx) {                                     // split sweep: k_events' per-segment clocks (words 3-5)
-            std::vector<double> cyc, wk, qq, ps;
-            for (int sgm = 0; sgm < d.nseg; ++sgm) {
-                cyc.push_back((double)st[(size_t)sgm * 8 + 3]); wk.push_back((double)st[(size_t)sgm * 8 + 4]);
-                qq.push_back((double)(st[(size_t)sgm * 8 + 5] >> 32)); ps.push_back((double)(st[(size_t)sgm * 8 + 5] & 0xffffffffull));
-            }
-            auto stat = [](std::vector<double> v, const char *nm) {
-                std::sort(v.begin(), v.end());
-                double sm = 0; for (double x : v) sm += x;
-                fprintf(stderr, "[stamps] k_events per segment %s: min %.0f  median %.0f  mean %.0f  p99 %.0f  max %.0f\n", nm, v.front(), v[v.size() / 2], sm / v.size(), v[(size_t)(v.size() * 0.99)], v.back());
-            };
-            stat(cyc, "cycles"); stat(wk, "cycles in walks"); stat(qq, "queue entries"); stat(ps, "walk passes");
-            std::vector<double> lc, ln;
-            for (int sgm = 0; sgm < d.nseg; ++sgm) { lc.push_back((double)(st[(size_t)sgm * 8 + 6] & ((1ull << 40) - 1))); ln.push_back((double)(st[(size_t)sgm * 8 + 6] >> 40)); }
-            stat(lc, "cycles in faces passes"); stat(ln, "faces passes");
-        }
-    }
+    NK_TRY(nk_stamps_report(ctx));
 #endif
-    const int32_t nd = *done;
-    if (!band_s.empty()) {                                   // the band rows of the steps that ran
-        const size_t rl = 4 * (size_t)S * ctx->band_B;
-        std::vector<double> br(band_s.size() * rl);
-        NK_HIP(hipMemcpyAsync(br.data(), ctx->band_rows_d, br.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        NK_HIP(hipStreamSynchronize(ctx->stream));
-        // a step whose migrants did not all fit their segments (k_deliver: halt word 2, the store grows before they are
-        // delivered) has tallied particles the pass could not see: no row for it
-        const int unseen = ctx->halt_words[2] ? nd - 1 : -1;
-        for (size_t r = 0; r < band_s.size(); ++r) {
-            if (band_s[r] >= nd || band_s[r] == unseen) continue;
-            ctx->band_rows.insert(ctx->band_rows.end(), br.begin() + r * rl, br.begin() + (r + 1) * rl);
-            ctx->band_steps.push_back(ctx->step + band_s[r]);
-        }
-    }
-    nk_batch_leave(ctx, nsteps, nd, tail_emit, relax0, nsteps > 0 && relax_flushed[0]);
-    float ms = 0.f;
-    double sk = 0.0, ek = 0.0, vk = 0.0;
-    const int nt = nd < nev ? nd : nev;
-    for (int s = 0; s < nt; ++s) {
-        NK_HIP(hipEventElapsedTime(&ms, ev[4 * s], ev[4 * s + 1])); ek += ms;
-        NK_HIP(hipEventElapsedTime(&ms, ev[4 * s + 1], ev[4 * s + 2])); sk += ms;
-        NK_HIP(hipEventElapsedTime(&ms, ev[4 * s + 2], ev[4 * s + 3])); vk += ms;
-    }
-    NK_HIP(hipEventElapsedTime(&ms, t0, t1));
-    if (nt > 0 && nd == nsteps) {
-        ctx->timing.step_kernel_ms = sk / nt;
-        ctx->timing.emit_kernel_ms = ek / nt;
-        ctx->timing.events_kernel_ms = vk / nt;
-        ctx->timing.total_ms = ms;
-    }
-    return NK_OK;
+    NK_TRY(nk_band_collect(ctx, band_s, *done));
+    nk_batch_leave(ctx, b, nsteps, *done);
+    return nk_batch_timing(ctx, nev, nsteps, *done);
 }
 
 // Small ensembles: many steps per launch (k_resident, nk_kernels.h).  OPT-IN (NK_RESIDENT=1): at 1e5 particles (31^3 x 6 modes)
@@ -2434,22 +2381,12 @@ static inline bool nk_want_resident(const nk_ctx *ctx) {
         if (box) { if (pid) NK_RESIDENT_CASE(true, true, lrec, STMT) else NK_RESIDENT_CASE(true, false, lrec, STMT) }   \
         else { if (pid) NK_RESIDENT_CASE(false, true, lrec, STMT) else NK_RESIDENT_CASE(false, false, lrec, STMT) }      \
     } while (0)
+// The resident path: one launch for every run of steps up to the next contains-check step.
 static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
     NkDev &d = ctx->d;
-    { int rcn_ = nk_normalize(ctx); if (rcn_) return rcn_; }
-    const int S = d.S, NB = d.NB;
-    const int HROW = NB + 2 * S + 8;
-    if (nsteps > ctx->hist_cap) {
-        if (ctx->hist) hipHostFree(ctx->hist);
-        ctx->hist = nullptr;
-        const int rows_alloc = nsteps < 1024 ? 1024 : nsteps;
-        NK_HIP(hipHostMalloc((void **)&ctx->hist, (size_t)rows_alloc * HROW * sizeof(double), hipHostMallocMapped));
-        ctx->hist_cap = rows_alloc;
-    }
-    ctx->timing.batches += 1;
-    ctx->emitted_for = -1;
-    memset(ctx->hist, 0, (size_t)nsteps * HROW * sizeof(double));
-    (void)nk_sweep_blocks(ctx);
+    const int NB = d.NB;
+    NkBatch b;
+    NK_TRY(nk_batch_enter(ctx, nsteps, b, true));     // (moves the segments down: the preludes then launch no k_anchor)
     const bool pid_ = (bool)d.pid, lrec_ = nk_want_lrec(ctx), box_ = d.box != 0;
     const size_t lds = nk_lds(ctx, true, pid_ ? 5 : 4);
     // every workgroup must be resident for the grid barrier: no more than the device holds at once (occupancy query), and no
@@ -2471,49 +2408,25 @@ static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h,
     G = std::max(1, G);
     // the tally rows, double-buffered by step parity (k_resident), live in `partials`: num_cu * 16 * NB doubles >= 2 G NBP, G <= 2 num_cu
     NK_ARG((size_t)2 * G * (size_t)((NB + 1) & ~1) <= (size_t)ctx->num_cu * 16 * NB, "nk_step_resident: tally rows exceed the partials buffer");
-    if (ctx->evpool.empty()) { ctx->evpool.resize(16 * 4 + 2); for (auto &e : ctx->evpool) NK_HIP(hipEventCreate(&e)); }
+    NK_TRY(nk_batch_events(ctx));
     hipEvent_t t0 = ctx->evpool[64], t1 = ctx->evpool[65];
-    const bool relax0 = ctx->pending_relax;
-    bool pending = ctx->pending_relax, flushed_first = false;
-    ctx->timing.emit_fused = 2;                                   // (2: emission inside the resident kernel)
     if (!ctx->rbar) NK_HIP(hipMalloc((void **)&ctx->rbar, (32 + 4096) * sizeof(unsigned int)));
     NK_HIP(hipEventRecord(t0, ctx->stream));
-    const int ce = ctx->params.contains_every;
-    int launches = 0;
     for (int k = 0; k < nsteps;) {
-        const int64_t stepno = ctx->step + k;
-        if (ce > 0 && (stepno % ce) == 0 && d.nS > 0) {
-            if (pending) {
-                k_relax<<<nk_sweep_grid(ctx), NK_WG, nk_lds(ctx, false), ctx->stream>>>(d, 1);
-                pending = false;
-                if (k == 0) flushed_first = true;
-            }
-            NK_GEOM_LAUNCH(k_contains, nk_sweep_grid(ctx), nk_lds(ctx, true), d, (uint32_t)stepno);
-        }
-        int n = nsteps - k;
-        if (ce > 0 && d.nS > 0) n = std::min<int64_t>(n, ce - (stepno % ce));
+        NK_TRY(nk_batch_prelude(ctx, b, k));
+        const NkGroupRec rec = nk_batch_rec(ctx, b, k);
+        int n = 1;                                                // the steps of this launch: up to the next contains-check step
+        while (k + n < nsteps && !nk_contains_step(ctx, ctx->step + k + n)) ++n;
         NK_HIP(hipMemsetAsync(ctx->rbar, 0, (32 + 1024 + 128) * sizeof(unsigned int), ctx->stream));     // the flags count from 1 in every launch
-        NK_RESIDENT_DISPATCH(box_, pid_, lrec_, (KERNEL<<<G, NK_WG, lds, ctx->stream>>>(d, (uint32_t)stepno, n, pending ? 1 : 0, ctx->params.flux_every,
-                                                                                       ctx->hist + (size_t)k * HROW, HROW, ctx->rbar)));
+        NK_RESIDENT_DISPATCH(box_, pid_, lrec_, (KERNEL<<<G, NK_WG, lds, ctx->stream>>>(d, rec.step, n, rec.do_relax, ctx->params.flux_every,
+                                                                                       rec.hist_row, nk_row(ctx).width(), ctx->rbar)));
         NK_HIP(hipGetLastError());
-        pending = true;
         k += n;
-        ++launches;
     }
     NK_HIP(hipEventRecord(t1, ctx->stream));
-    const size_t hbytes = (size_t)nsteps * HROW * sizeof(double);
     NK_HIP(hipStreamSynchronize(ctx->stream));
-    h.resize((size_t)nsteps * HROW);
-    memcpy(h.data(), ctx->hist, hbytes);
-    {   // the halt words as the last step that ran left them (its update wrote them behind the row); no row: ask the device
-        int last_ = -1;
-        for (int q_ = 0; q_ < nsteps && h[(size_t)q_ * HROW + NB + 2 * S + 1] != 0.0; ++q_) last_ = q_;
-        if (last_ >= 0) for (int k_ = 0; k_ < 4; ++k_) ctx->halt_words[k_] = (int32_t)h[(size_t)last_ * HROW + NB + 2 * S + 4 + k_];
-        else NK_HIP(hipMemcpy(ctx->halt_words, d.halt, 16, hipMemcpyDeviceToHost));
-    }
-    int32_t nd = 0;
-    while (nd < nsteps && h[(size_t)nd * HROW + NB + 2 * S + 1] != 0.0) ++nd;
-    *done = nd;
+    NK_TRY(nk_batch_collect(ctx, nsteps, h, done));
+    const int32_t nd = *done;
     if (getenv("NK_VERBOSE") && ctx->timing.batches % 8 == 2) {   // developer probe: the clock marks of the launch's last step (10 ns ticks)
         unsigned long long m[12];
         NK_HIP(hipMemcpy(m, ctx->rbar + 8, sizeof(m), hipMemcpyDeviceToHost));
@@ -2522,8 +2435,7 @@ static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h,
                     (m[1] - m[0]) * 0.01, (m[2] - m[1]) * 0.01, (m[3] - m[2]) * 0.01, (m[4] - m[3]) * 0.01, (m[5] - m[4]) * 0.01, (m[6] - m[5]) * 0.01,
                     (m[9] - m[8]) * 0.01, (m[10] - m[9]) * 0.01, (m[11] - m[10]) * 0.01);
     }
-    if (nd > 0) ctx->pending_relax = true;
-    else ctx->pending_relax = relax0 && !flushed_first;
+    nk_batch_leave(ctx, b, nsteps, nd);
     float ms = 0.f;
     NK_HIP(hipEventElapsedTime(&ms, t0, t1));
     if (nd == nsteps && nd > 0) {
@@ -2532,10 +2444,17 @@ static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h,
         ctx->timing.events_kernel_ms = 0.0;
         ctx->timing.total_ms = ms;
     }
-    (void)launches;
     return NK_OK;
 }
 
+// What the side tallies that are on derive from the store, again after anything that changed it: the field's scales, the groups'
+// table in the segments' order, the mode tally's.
+static int nk_tallies_refresh(nk_ctx *ctx) {
+    if (ctx->field.on) NK_TRY(nk_field_refresh(ctx));
+    if (ctx->fgroups.on) NK_TRY(nk_fgroups_refresh(ctx));
+    if (ctx->modes.on) NK_TRY(nk_modes_refresh(ctx));
+    return NK_OK;
+}
 // nk_step in three parts, shared with nk_group_step: what runs before the first batch of a call ...
 static int nk_step_begin(nk_ctx *ctx) {
     int rc = nk_check_ready(ctx);
@@ -2547,10 +2466,7 @@ static int nk_step_begin(nk_ctx *ctx) {
     ctx->stepped = true;
     ctx->band_rows.clear();
     ctx->band_steps.clear();
-    if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;
-    if (ctx->fgroups.on && (rc = nk_fgroups_refresh(ctx))) return rc;
-    if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;
-    return NK_OK;
+    return nk_tallies_refresh(ctx);
 }
 struct NkStepRun {
     int32_t s_out = 0;     // rows delivered so far
@@ -2563,29 +2479,29 @@ struct NkStepRun {
 static int nk_step_consume(nk_ctx *ctx, int32_t nsteps, nk_tally *out, NkStepRun &run, const std::vector<double> &h, int32_t nd) {
     NkDev &d = ctx->d;
     const int S = d.S, R = d.R, NB = d.NB;
-    const int HROW = NB + 2 * S + 8;
+    const NkRow at = nk_row(ctx);
     int rc = NK_OK;
     for (int s = 0; s < nd; ++s) {
-        const double *row = &h[(size_t)s * HROW];
-        if (row[NB + 2 * S + 3] != 0.0) run.overflow |= (int)row[NB + 2 * S + 3];
+        const double *row = &h[(size_t)s * at.width()];
+        if (row[at.overflow()] != 0.0) run.overflow |= (int)row[at.overflow()];
         if (!out) continue;
         const size_t q = (size_t)(run.s_out + s);
         if (out->E_raw) memcpy(out->E_raw + q * S, row, S * 8);
         if (out->N_sv) memcpy(out->N_sv + q * S, row + S, S * 8);
         if (out->flux_raw) {
-            if (row[NB + 2 * S] != 0.0) memcpy(out->flux_raw + q * 3 * S, row + 2 * S, 3 * S * 8);
+            if (row[at.flux()] != 0.0) memcpy(out->flux_raw + q * 3 * S, row + 2 * S, 3 * S * 8);
             else for (int k = 0; k < 3 * S; ++k) out->flux_raw[q * 3 * S + k] = NAN;
         }
         if (out->N_leaving && R) memcpy(out->N_leaving + q * R, row + 5 * S, R * 8);
         if (out->res_energy && R) memcpy(out->res_energy + q * R, row + 5 * S + R, R * 8);
         if (out->res_flux && R) memcpy(out->res_flux + q * 3 * R, row + 5 * S + 2 * R, 3 * R * 8);
         if (out->N_emitted) out->N_emitted[q] = row[NB - 1];
-        if (out->T_sv) memcpy(out->T_sv + q * S, row + NB, S * 8);
-        if (out->E_sv) memcpy(out->E_sv + q * S, row + NB + S, S * 8);
+        if (out->T_sv) memcpy(out->T_sv + q * S, row + at.T(), S * 8);
+        if (out->E_sv) memcpy(out->E_sv + q * S, row + at.E(), S * 8);
     }
     if (nd > 0) {
-        const double *last = &h[(size_t)(nd - 1) * HROW];
-        nk_track_T(ctx, last + NB, S);
+        const double *last = &h[(size_t)(nd - 1) * at.width()];
+        nk_track_T(ctx, last + at.T(), S);
         double live = 0.0;
         for (int k = 0; k < S; ++k) live += last[S + k];
         ctx->timing.live = (int64_t)live;
@@ -2626,9 +2542,7 @@ static int nk_step_consume(nk_ctx *ctx, int32_t nsteps, nk_tally *out, NkStepRun
             if ((rc = nk_ensure_migration(ctx, want))) return rc;
         }
         if ((rc = nk_update_tau_window(ctx, false))) return rc;
-        if (ctx->field.on && (rc = nk_field_refresh(ctx))) return rc;     // the store has grown: the field's scales follow
-        if (ctx->fgroups.on && (rc = nk_fgroups_refresh(ctx))) return rc; // ... and the groups' table in the segments' order
-        if (ctx->modes.on && (rc = nk_modes_refresh(ctx))) return rc;     // ... and the mode tally's
+        if ((rc = nk_tallies_refresh(ctx))) return rc;                   // the store has grown
     }
     return NK_OK;
 }
@@ -2691,7 +2605,7 @@ int nk_step(nk_ctx *ctx, int32_t nsteps, nk_tally *out) {
 // a device copy of the members' NkDevs (refreshed once per call: the lifetime window or a grown store change them), the prefix
 // tables of the two grids, and one record per (step, member) of a call; everything else -- particles, tables, tallies, history
 // rows, halt words, the alternating walk, the emission that ran ahead, the deferred relaxation -- stays the member's own and is
-// kept exactly as nk_step_batch keeps it, so that a member can be stepped alone between group calls.
+// kept by the code that keeps it for nk_step_batch (NkBatch, nk_batch_*), so that a member can be stepped alone between group calls.
 struct nk_group {
     int R = 0;
     std::vector<nk_ctx *> m;
@@ -2865,15 +2779,21 @@ int nk_group_info(nk_group *g, nk_group_report *out) {
     return NK_OK;
 }
 
+// a member's error becomes the group's: "member r: ..."
+static int nk_member_failed(nk_group *g, int r, int rc) {
+    g->err = "member " + std::to_string(r) + ": " + g->m[(size_t)r]->err;
+    return rc;
+}
 // nk_step_batch for all members at once, within the grouped path's scope (nk_group_scope): per step one k_sweep_group and one
 // k_tail_group on `stream` (every member's ctx->stream is that stream during the call), one wait for the whole call.  hs[r] / nds[r]:
 // member r's history rows and how many of its steps ran (a member that halted stops alone).
 static int nk_group_batch(nk_group *g, const NkGroupPlan &plan, hipStream_t stream, int32_t nsteps, std::vector<std::vector<double>> &hs,
                           std::vector<int32_t> &nds) {
     const int R = g->R;
+    int rc = NK_OK;
     const NkGroupKey &key = plan.key;
     const size_t lds_w = plan.lds_w, lds_t = plan.lds_t;
-    const int S = key.S, NB = key.NB, HROW = NB + 2 * S + 8;
+    const int NB = key.NB;
     NkGroupHead *head = reinterpret_cast<NkGroupHead *>(g->stage);
     NkDev *devs = reinterpret_cast<NkDev *>(g->stage + sizeof(NkGroupHead));
     for (int k = 0; k <= NK_GROUP_MAX; ++k) head->pre_sweep[k] = head->pre_tail[k] = INT32_MAX;
@@ -2888,54 +2808,20 @@ static int nk_group_batch(nk_group *g, const NkGroupPlan &plan, hipStream_t stre
         NK_GHIP(hipHostMalloc((void **)&g->recs_h, (size_t)cap * R * sizeof(NkGroupRec), hipHostMallocDefault));
         g->recs_cap = cap;
     }
-    struct Member { int g_sweep = 0, g_emit = 0; bool alt = false, pending = false, relax0 = false, flushed0 = false, emitted_ahead = false, tail_emit = false; };
-    std::vector<Member> mem((size_t)R);
+    std::vector<NkBatch> mem((size_t)R);
     int grid_sweep = 0, grid_tail = 0;
     for (int r = 0; r < R; ++r) {
         nk_ctx *ctx = g->m[r];
-        NkDev &d = ctx->d;
-        Member &me = mem[(size_t)r];
-        if (nk_batch_hist(ctx, nsteps)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
-        (void)nk_sweep_blocks(ctx);
-        me.g_sweep = ctx->g_sweep < (d.nseg + 3) / 4 ? ctx->g_sweep : (d.nseg + 3) / 4;
-        me.tail_emit = d.R > 0;                          // (not 'one_to_one', NK_NO_TAIL_EMIT unset: nk_group_scope)
-        me.g_emit = me.tail_emit ? (ctx->num_cu * 8 < (d.nseg + 3) / 4 ? ctx->num_cu * 8 : (d.nseg + 3) / 4) : 0;
-        d.tree_lds_fam0 = d.tree_nfam; d.tree_lds_off = 0;
-        me.relax0 = me.pending = ctx->pending_relax;
-        me.emitted_ahead = me.tail_emit && ctx->emitted_for == ctx->step;
-        ctx->emitted_for = -1;
-        ctx->timing.emit_fused = me.tail_emit ? 1 : 0;
-        me.alt = d.seg_lo && !getenv("NK_NO_ALTERNATE");
-        if (!me.alt) {
-            const bool launches = ctx->walked && d.seg_lo;
-            if (nk_normalize(ctx)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
-            if (launches) g->rep.member_launches += 1;
-        }
-        d.down = 0;
+        NkBatch &me = mem[(size_t)r];
+        if ((rc = nk_batch_enter(ctx, nsteps, me, false, &g->rep.member_launches))) return nk_member_failed(g, r, rc);
         head->pre_sweep[r] = grid_sweep; head->pre_tail[r] = grid_tail; head->rows[r] = me.g_sweep;
         grid_sweep += me.g_sweep;
-        grid_tail += NB + me.g_emit;
-        devs[r] = d;
+        grid_tail += NB + (me.tail_emit ? me.g_emit : 0);
+        devs[r] = ctx->d;
+        // the records of the whole call: what nk_step_batch passes to each step's launches
+        for (int s = 0; s < nsteps; ++s) g->recs_h[(size_t)s * R + r] = nk_batch_rec(ctx, me, s);
     }
     head->pre_sweep[R] = grid_sweep; head->pre_tail[R] = grid_tail;
-    // the records of the whole call: what nk_step_batch passes to each step's launches
-    for (int r = 0; r < R; ++r) {
-        nk_ctx *ctx = g->m[r];
-        const NkDev &d = ctx->d;
-        bool pending = mem[(size_t)r].pending;
-        for (int s = 0; s < nsteps; ++s) {
-            const int64_t stepno = ctx->step + s;
-            if (key.contains_every > 0 && (stepno % key.contains_every) == 0 && d.nS > 0) pending = false;   // (k_relax runs ahead of k_contains)
-            NkGroupRec &rec = g->recs_h[(size_t)s * R + r];
-            rec.step = (uint32_t)stepno;
-            rec.do_relax = pending ? 1 : 0;
-            rec.do_flux = (key.flux_every > 0 && ((stepno + 1) % key.flux_every) == 0) ? 1 : 0;
-            rec.down = mem[(size_t)r].alt ? (int32_t)(stepno & 1) : 0;
-            rec.hist_row = ctx->hist + (size_t)s * HROW;
-            rec.acc = ctx->acc;
-            pending = true;
-        }
-    }
     NkGroupHead *head_d = reinterpret_cast<NkGroupHead *>(g->dev);
     NkDev *devs_d = reinterpret_cast<NkDev *>(g->dev + sizeof(NkGroupHead));
     NK_GHIP(hipMemcpyAsync(g->dev, g->stage, sizeof(NkGroupHead) + (size_t)R * sizeof(NkDev), hipMemcpyHostToDevice, stream));
@@ -2948,21 +2834,15 @@ static int nk_group_batch(nk_group *g, const NkGroupPlan &plan, hipStream_t stre
         for (int r = 0; r < R; ++r) {                    // what a step may need per member: the prelude of a contains_check step ...
             nk_ctx *ctx = g->m[r];
             NkDev &d = ctx->d;
-            Member &me = mem[(size_t)r];
-            const int64_t stepno = ctx->step + s;
-            {
-                bool fl_ = false;
-                if (nk_batch_prelude(ctx, stepno, me.pending, fl_, &g->rep.member_launches)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
-                if (fl_ && s == 0) me.flushed0 = true;
-            }
+            NkBatch &me = mem[(size_t)r];
+            if ((rc = nk_batch_prelude(ctx, me, s, &g->rep.member_launches))) return nk_member_failed(g, r, rc);
             // ... and an emission that no tail has run ahead (the first step after anything that changed the store or the tables)
             if (d.R > 0 && !me.emitted_ahead) {
-                NK_EMIT_LAUNCH(k_emit, me.g_emit, nk_lds(ctx, true, 1), d, (uint32_t)stepno);
+                NK_EMIT_LAUNCH(k_emit, me.g_emit, nk_lds(ctx, true, 1), d, (uint32_t)(ctx->step + s));
                 g->rep.member_launches += 1;
             }
             if (me.alt) ctx->walked = true;
             me.emitted_ahead = me.tail_emit;
-            me.pending = true;
         }
         if (s < nev) NK_GHIP(hipEventRecord(ev[3 * s], stream));
         NK_GHIP(nk_group_launch_sweep(key.kind, grid_sweep, lds_w, stream, head_d, devs_d, g->recs_d + (size_t)s * R));
@@ -2982,11 +2862,10 @@ static int nk_group_batch(nk_group *g, const NkGroupPlan &plan, hipStream_t stre
     bool all_ran = true;
     for (int r = 0; r < R; ++r) {
         nk_ctx *ctx = g->m[r];
-        const Member &me = mem[(size_t)r];
         int32_t nd = 0;
-        if (nk_batch_collect(ctx, nsteps, hs[(size_t)r], &nd)) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return NK_ERR_HIP; }
+        if ((rc = nk_batch_collect(ctx, nsteps, hs[(size_t)r], &nd))) return nk_member_failed(g, r, rc);
         nds[(size_t)r] = nd;
-        nk_batch_leave(ctx, nsteps, nd, me.tail_emit, me.relax0, me.flushed0);
+        nk_batch_leave(ctx, mem[(size_t)r], nsteps, nd);
         if (nd < nsteps) all_ran = false;
     }
     float ms = 0.f;
@@ -3018,7 +2897,7 @@ int nk_group_step(nk_group *g, int32_t nsteps, nk_tally *outs) {
     for (int r = 0; r < R; ++r) { own[(size_t)r] = g->m[r]->stream; g->m[r]->stream = stream; }
     auto leave = [&](int code) { for (int r = 0; r < R; ++r) g->m[r]->stream = own[(size_t)r]; return code; };
     for (int r = 0; r < R; ++r)
-        if ((rc = nk_step_begin(g->m[r]))) { g->err = "member " + std::to_string(r) + ": " + g->m[r]->err; return leave(rc); }
+        if ((rc = nk_step_begin(g->m[r]))) return leave(nk_member_failed(g, r, rc));
     std::vector<std::vector<double>> hs((size_t)R);
     std::vector<int32_t> nds((size_t)R, 0);
     if ((rc = nk_group_batch(g, plan, stream, nsteps, hs, nds))) return leave(rc);
@@ -3028,21 +2907,18 @@ int nk_group_step(nk_group *g, int32_t nsteps, nk_tally *outs) {
         NkStepRun run;
         nk_tally *out = outs ? &outs[r] : nullptr;
         const int64_t halts0 = ctx->timing.halts;
-        if ((rc = nk_step_consume(ctx, nsteps, out, run, hs[(size_t)r], nds[(size_t)r]))) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return leave(rc); }
+        if ((rc = nk_step_consume(ctx, nsteps, out, run, hs[(size_t)r], nds[(size_t)r]))) return leave(nk_member_failed(g, r, rc));
         if (ctx->timing.halts != halts0 && !g->halted[(size_t)r]) { g->halted[(size_t)r] = 1; g->rep.halted += 1; }
         if (run.s_out < nsteps) {                        // a straggler: its store has grown, it takes its remaining steps alone
             if (!g->alone[(size_t)r]) { g->alone[(size_t)r] = 1; g->rep.finished_alone += 1; }
             std::vector<double> h;
             while (run.s_out < nsteps) {
                 int32_t nd = 0;
-                if ((rc = nk_step_batch(ctx, nsteps - run.s_out, h, &nd)) || (rc = nk_step_consume(ctx, nsteps, out, run, h, nd))) {
-                    g->err = "member " + std::to_string(r) + ": " + ctx->err;
-                    return leave(rc);
-                }
+                if ((rc = nk_step_batch(ctx, nsteps - run.s_out, h, &nd)) || (rc = nk_step_consume(ctx, nsteps, out, run, h, nd))) return leave(nk_member_failed(g, r, rc));
                 g->rep.member_launches += 2 * (int64_t)nd;
             }
         }
-        if ((rc = nk_step_end(ctx, run.overflow))) { g->err = "member " + std::to_string(r) + ": " + ctx->err; return leave(rc); }
+        if ((rc = nk_step_end(ctx, run.overflow))) return leave(nk_member_failed(g, r, rc));
     }
     return leave(NK_OK);
 }
@@ -3054,7 +2930,7 @@ int nk_download_particles(nk_ctx *ctx, int64_t capacity, double *x, double *y, d
     NkDev &d = ctx->d;
     *N_out = 0;
     if (d.cap == 0) return NK_OK;
-    if (ctx->have_material && ctx->have_sv && ctx->have_mesh) { int rc = nk_flush_relax(ctx, 0); if (rc) return rc; }
+    if (ctx->have_material && ctx->have_sv && ctx->have_mesh) NK_TRY(nk_flush_relax(ctx, 0));
     NkHostParticles h;
     int rc = nk_gather_live(ctx, h, capacity != 0);
     if (rc) return rc;
@@ -3686,7 +3562,7 @@ int nk_calibrate_stream(nk_ctx *ctx, int32_t launches, int64_t *bytes_read, int6
     NK_HIP(hipSetDevice(ctx->device));
     NK_HIP(hipStreamSynchronize(ctx->stream));
     NkHostParticles h;
-    { int rc = nk_gather_live(ctx, h, false); if (rc) return rc; }
+    NK_TRY(nk_gather_live(ctx, h, false));
     const int64_t ns = (int64_t)h.x.size();
     for (int k = 0; k < launches; ++k) k_cal_stream<<<nk_sweep_grid(ctx), NK_WG, 0, ctx->stream>>>(ctx->d);
     NK_HIP(hipGetLastError());

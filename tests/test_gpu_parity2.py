@@ -434,6 +434,43 @@ def test_resident_long_run_every_row(store, grid, monkeypatch):
     compare_by_pid(res.download(), sim, pos_atol=TOL_X_LONG)
 
 
+@pytest.mark.parametrize('store', ['box', 'cached'])
+def test_resident_and_launch_calls_hand_over(store, monkeypatch):
+    """One engine stepped through BOTH paths in turn: calls of 7, 1, 60, 45 and 17 steps, the 1st, 3rd and 5th by the resident
+    kernel (NK_RESIDENT=1), the others by the launch path (the 45-step call crosses the contains_check at step 100), and a
+    download after the third call.  What a call hands to the next -- the deferred relaxation, the emission that ran ahead in the
+    last tail, the segments an alternating walk has left off slot 0 -- is kept by the same code for both paths, so the run equals
+    one 130-step call of the launch path on the same seed."""
+    if store == 'cached':
+        monkeypatch.setenv('NK_NO_BOX', '1')
+    ct = case_tables('ttp')
+    pos, mode, occ, counter = random_population(ct, 30000, seed=5)
+    a = make_engine(ct, pos, mode, occ, counter, seed=42)
+    b = make_engine(ct, pos, mode, occ, counter, seed=42)
+    assert a.timing()['box_store'] == (1 if store == 'box' else 0)
+    tb = b.step(130)
+    assert b.timing()['emit_fused'] == 1
+    rows = []
+    for call, n in enumerate([7, 1, 60, 45, 17]):
+        resident = call % 2 == 0
+        if resident:
+            monkeypatch.setenv('NK_RESIDENT', '1')
+        rows.append(a.step(n))
+        assert a.timing()['emit_fused'] == (2 if resident else 1), call
+        if resident:
+            monkeypatch.delenv('NK_RESIDENT')
+        if call == 2:
+            a.download()
+    for k in ('N_sv', 'N_emitted', 'N_leaving'):
+        assert np.array_equal(tb[k], np.concatenate([r[k] for r in rows])), k
+    assert allclose(tb['T_sv'], np.concatenate([r['T_sv'] for r in rows]), rtol=0, atol=TOL_T)
+    assert_runs_equal(tb, {k: np.concatenate([r[k] for r in rows]) for k in tb})
+    pa, pb = a.download(), b.download()
+    oa, ob = np.argsort(pa['pid']), np.argsort(pb['pid'])
+    assert np.array_equal(pa['pid'][oa], pb['pid'][ob]) and np.array_equal(pa['mode'][oa], pb['mode'][ob])
+    assert allclose(pa['positions'][oa], pb['positions'][ob], rtol=0, atol=TOL_X) and rel_err(pa['occupation'][oa], pb['occupation'][ob]) < TOL_OCC
+
+
 @pytest.mark.parametrize('case', ['ttp', 'ttrrp'])
 def test_box_store_against_the_references_event_rule(case):
     """The box store (events read off the position) against the oracle on the reference's own rule (the cached n_timesteps,
