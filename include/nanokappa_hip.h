@@ -456,7 +456,13 @@ int nk_classify(nk_ctx *ctx, int64_t n, const double *x, int32_t *id);          
 int nk_eval(nk_ctx *ctx, int32_t what, int64_t n, const double *a, const int32_t *mode, double *out);
 /* what: 0 occupation(T=a[i], omega[mode[i]]) Phonon.py:338; 1 lifetime(T=a[i], mode[i]) Phonon.py:336;
  *       2 T(E=a[i]) Phonon.py:387; 3 E(T=a[i]) Phonon.py:390; 4 per-particle T at x=a[3i..] Population.py:696;
- *       5 the kernels' own exp(a[i]) */
+ *       5 the kernels' own exp(a[i]); 6 their short series exp(a[i]), |a[i]| <= 1/8; 7 their reciprocal 1 / a[i];
+ *       8 their relaxation of one particle, a[4i..] = x, y, z, occupation, of mode[i], with the context's dt, subvolume
+ *         temperatures and lifetimes (Population.py:1701-1710); 64 consecutive i make one wave, which picks the exponential */
+/* The segment of the particle store that holds the particles of every mode (seg[M]) and the number of segments, once particles
+ * are uploaded.  nk_download_particles returns the segments one after another, each in slot order, and a wave of the sweep takes
+ * 64 consecutive slots of one segment: with this map a test can tell which particles shared a wave. */
+int nk_mode_segments(nk_ctx *ctx, int32_t *seg, int32_t *nseg);
 int nk_reflect(nk_ctx *ctx, int64_t n, const int32_t *facet, const int32_t *mode_in, const double *col_pos,
                const double *n_in, const double *omega_in, const double *r_spec, const double *r_deg,
                const double *r_diff, int32_t *mode_out, double *n_out, double *omega_out); /* Population.py:941-1015 */

@@ -3526,16 +3526,25 @@ int nk_classify(nk_ctx *ctx, int64_t n, const double *x, int32_t *id) {
     return NK_OK;
 }
 int nk_eval(nk_ctx *ctx, int32_t what, int64_t n, const double *a, const int32_t *mode, double *out) {
-    NK_ARG(ctx && ctx->have_material && n > 0 && a && out && what >= 0 && what <= 5, "nk_eval: bad arguments");
-    NK_ARG(what > 1 || mode, "nk_eval: mode required");
+    NK_ARG(ctx && ctx->have_material && n > 0 && a && out && what >= 0 && what <= 8, "nk_eval: bad arguments");
+    NK_ARG((what > 1 && what != 8) || mode, "nk_eval: mode required");
     NK_ARG(ctx->have_sv, "nk_eval: subvolumes required");
+    if (mode) for (int64_t i = 0; i < n; ++i) NK_ARG(mode[i] >= 0 && mode[i] < ctx->d.M, "nk_eval: mode index out of range");
     NK_HIP(hipSetDevice(ctx->device));
-    const int64_t na = what == 4 ? 3 * n : n;
+    const int64_t na = what == 4 ? 3 * n : (what == 8 ? 4 * n : n);
     NK_BUF(double, da, a, na); NK_BUF(int32_t, dm, mode, n); NK_BUF(double, dout, nullptr, n);
     k_tap_eval<<<(int)((n + NK_WG - 1) / NK_WG), NK_WG, nk_lds(ctx, false), ctx->stream>>>(ctx->d, what, n, da.p, mode ? dm.p : nullptr, dout.p);
     NK_HIP(hipGetLastError());
     NK_HIP(hipStreamSynchronize(ctx->stream));
     NK_HIP(dout.get(out, n));
+    return NK_OK;
+}
+int nk_mode_segments(nk_ctx *ctx, int32_t *seg, int32_t *nseg) {
+    NK_ARG(ctx && seg && nseg, "nk_mode_segments: NULL argument");
+    const NkDev &d = ctx->d;
+    NK_ARG(d.cap > 0 && d.part && ctx->map_nseg == d.nseg && ctx->h_m2s.size() == (size_t)d.M, "nk_mode_segments: no particle store with partitioned modes");
+    for (int m = 0; m < d.M; ++m) seg[m] = nk_mode_seg(ctx, m, d.nseg);
+    *nseg = d.nseg;
     return NK_OK;
 }
 int nk_reflect(nk_ctx *ctx, int64_t n, const int32_t *facet, const int32_t *mode_in, const double *col_pos,

@@ -2401,6 +2401,16 @@ NK_KERNEL_LINKAGE __global__ __launch_bounds__(NK_WG) void k_tap_eval(NkDev d, i
         case 2: out[i] = nk_T_of_E(d, a[i]); break;
         case 3: out[i] = nk_E_of_T(d, a[i]); break;
         case 5: out[i] = nk_exp(a[i]); break;
+        case 6: out[i] = nk_exp_small(a[i]); break;
+        case 7: out[i] = nk_rcp(a[i]); break;
+        case 8: {   // nk_relax of one particle {x, y, z, occ}; its exponential is chosen per wave: the lanes are 64 consecutive i
+            const NkMode *rec = d.modetab + mode[i];
+            NkTauWin tw; tw.load(d, false);
+            NkSegModes sm; sm.rec = d.modetab; sm.gm = nullptr; sm.nl = 0; sm.estride = 1; sm.eoff = 0;     // the stored index is the mode
+            const double4 ra = make_double4(rec->omega, rec->vx, rec->vy, rec->vz), rb = make_double4(rec->E0, rec->tau[0], rec->tau[1], rec->tau[2]);
+            out[i] = nk_relax(d, L, tw, ra, rb, a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3], sm, mode[i]);
+            break;
+        }
         default: { double invT; out[i] = nk_interp_T(d, L.tb, a[3 * i], a[3 * i + 1], a[3 * i + 2], invT); break; }
     }
 }

@@ -84,7 +84,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_reservoirs', 'nk_set_rough', 'nk_set_params', 'nk_reserve', 'nk_upload_particles',
            'nk_init_boundaries', 'nk_step', 'nk_download_particles', 'nk_get_subvol_temperature',
            'nk_set_subvol_temperature', 'nk_get_step', 'nk_get_timing', 'nk_comm_unique_id', 'nk_comm_init',
-           'nk_find_boundary', 'nk_classify', 'nk_eval', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
+           'nk_find_boundary', 'nk_classify', 'nk_eval', 'nk_mode_segments', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
            'nk_specular_begin', 'nk_specular_pairs', 'nk_specular_end', 'nk_rough_begin', 'nk_rough_pairs', 'nk_rough_finish',
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
@@ -178,6 +178,7 @@ def load_library():
     L.nk_find_boundary.argtypes = [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, c_ip]
     L.nk_classify.argtypes = [C.c_void_p, C.c_int64, c_dp, c_ip]
     L.nk_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_dp, c_ip, c_dp]
+    L.nk_mode_segments.argtypes = [C.c_void_p, c_ip, C.POINTER(C.c_int32)]
     L.nk_reflect.argtypes = [C.c_void_p, C.c_int64, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp, c_dp]
     L.nk_uniform2.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, c_dp, c_dp]
     L.nk_calibrate_stream.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -838,13 +839,21 @@ class Engine(object):
         return out
 
     def eval(self, what, a, mode=None):
-        code = {'occupation': 0, 'lifetime': 1, 'T_of_E': 2, 'E_of_T': 3, 'interp_T': 4, 'exp': 5}[what]
+        code = {'occupation': 0, 'lifetime': 1, 'T_of_E': 2, 'E_of_T': 3, 'interp_T': 4, 'exp': 5, 'exp_small': 6, 'rcp': 7,
+                'relax': 8}[what]                      # 'relax': a[n, 4] = x, y, z, occupation
         a = _d(a)
         n = a.shape[0]
         m = None if mode is None else _i(mode)
         out = np.zeros(n)
         self._ck(self.L.nk_eval(self.h, code, n, _p(a), _p(m, c_ip), _p(out)), 'nk_eval')
         return out
+
+    def mode_segments(self):
+        """(segment of the particle store that holds every mode's particles [M], number of segments).  download() returns the
+        segments one after another, and a wave of the sweep takes 64 consecutive particles of one segment."""
+        seg, n = np.zeros(self.M, dtype=np.int32), C.c_int32(0)
+        self._ck(self.L.nk_mode_segments(self.h, _p(seg, c_ip), C.byref(n)), 'nk_mode_segments')
+        return seg, int(n.value)
 
     def reflect(self, facet, mode_in, col_pos, n_in, omega_in, r_spec, r_deg, r_diff):
         f, m, c = _i(facet), _i(mode_in), _d(col_pos)

@@ -127,13 +127,26 @@ def rel_row(a, b, tag=None, bound=None, depth=1):
     return r
 
 
+def ulp_err(got, hi, lo=0.0, tag=None, bound=None, depth=1):
+    """max |got - (hi + lo)| / spacing(hi): the error of `got` in ulps of the reference, whose exact value is given as the double
+    `hi` it rounds to plus the remainder `lo` (a reference rounded to double alone would blur the figure by half an ulp).
+    Recorded like rel_err."""
+    got, hi, lo = (np.asarray(v, dtype=float) for v in (got, hi, lo))
+    with np.errstate(invalid='ignore', over='ignore'):
+        e = np.abs((got - hi) - lo) / np.spacing(np.abs(hi))
+    e = np.where(np.isnan(e), np.inf, e)
+    r = float(np.max(e)) if e.size else 0.0
+    _record('ulp', r, None if bound is None else 'ulp %g' % bound, depth=depth + 1, tag=tag)
+    return r
+
+
 def write_margins(path):
     if not MARGINS:
         return
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, 'w') as f:
         f.write('# largest deviation seen at each comparison of reals in this `pytest -m gpu` run (tests/util.py)\n')
-        f.write('# site | kind (rel = max |a-b|/|b|, abs = max |a-b|, row = max |a-b| / max |b|) | worst | bound in the test | calls | tests\n')
+        f.write('# site | kind (rel = max |a-b|/|b|, abs = max |a-b|, row = max |a-b| / max |b|, ulp = max |a-b| / spacing(b)) | worst | bound in the test | calls | tests\n')
         for k in sorted(MARGINS):
             m = MARGINS[k]
             f.write('%-44s %-4s %-12.3e %-24s %5d  %s\n' % (k, m['kind'], m['worst'], m['bound'] or '(see the test)', m['calls'],
@@ -165,6 +178,31 @@ def case_tables(case='ttrrp', model='velocity'):
     return out
 
 
+def _pow2(s):
+    m, _ = np.frexp(float(s))
+    return m == 0.5
+
+
+def scaled_case(ct, dt=1.0, v_scale=1.0, tau_scale=1.0):
+    """A copy of a case_tables() / case_from_args() dict for the time step `dt` on a material whose group velocities are
+    v_scale and whose lifetimes tau_scale times the case's: group_vel * v_scale, lifetime * tau_scale (entries <= 0 mark
+    inactive modes and stay), enter_prob * (dt * v_scale) (enter_prob = max(0, v.n) dt / thickness, made with dt = 1).  The
+    scales are powers of two, so every product is the exact double.  The rough tables (specularity, specular map, roulette)
+    depend on directions and wavevectors, not on |v|, and stay."""
+    assert _pow2(dt) and _pow2(v_scale) and _pow2(tau_scale), 'powers of two only: the scaled tables must be exact'
+    out = dict(ct)
+    tb = dict(ct['tables'])
+    v, tau = np.asarray(tb['group_vel'], dtype=float), np.asarray(tb['lifetime'], dtype=float)
+    tb['group_vel'] = v * v_scale
+    tb['lifetime'] = np.where(tau > 0, tau * tau_scale, tau)
+    out['tables'] = tb
+    out['enter_prob'] = ct['enter_prob'] * (dt * v_scale)
+    for a, b, f in ((tb['group_vel'], v, v_scale), (tb['lifetime'][tau > 0], tau[tau > 0], tau_scale),
+                    (out['enter_prob'], ct['enter_prob'], dt * v_scale)):
+        assert np.all(np.isfinite(a)) and np.array_equal(a / f, b), 'a scaled table is not exact'
+    return out
+
+
 def random_population(ct, n, seed, T0=298.0):
     """Uniform positions in the box, uniformly random active modes, n = BE(T0) (Population.py:127-144, :280)."""
     rng = np.random.default_rng(seed)
@@ -179,7 +217,7 @@ def random_population(ct, n, seed, T0=298.0):
 
 
 def make_oracle_sim(ct, pos, mode, occ, counter, seed, cap=None, interp=1, T0=298.0, emit_scale=1.0, gen=0,
-                    ids_from_state=False, res_T=None, box='auto'):
+                    ids_from_state=False, res_T=None, box='auto', dt=1.0):
     """box='auto': the oracle decides events the way the engine does on this mesh (box rule on axis-aligned boxes, see
     oracle/nk_oracle.h nko_params::box); box=False: the reference's cached rule."""
     import sys
@@ -200,7 +238,7 @@ def make_oracle_sim(ct, pos, mode, occ, counter, seed, cap=None, interp=1, T0=29
     else:
         z = np.zeros(0)
         rough = O.make_rough(np.zeros(0, dtype=np.int32), z, np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.int32), z)
-    par = O.make_params(dt=1.0, particle_density=ct['particle_density'], seed=seed, ids_from_state=ids_from_state)
+    par = O.make_params(dt=dt, particle_density=ct['particle_density'], seed=seed, ids_from_state=ids_from_state)
     n = pos.shape[0]
     store = O.ParticleStore(cap or (2 * n + 4096))
     store.load(pos, mode, occ)
@@ -297,7 +335,7 @@ def first_n_leaving(enter_prob):
 
 
 def make_engine(ct, pos, mode, occ, counter, seed, interp=1, T0=298.0, emit_scale=1.0, flux_every=10,
-                contains_every=100, device=0, gen=0, pid_offset=0, comm=None, track_ids=True, res_T=None):
+                contains_every=100, device=0, gen=0, pid_offset=0, comm=None, track_ids=True, res_T=None, dt=1.0):
     """track_ids=True: the engine keeps the 64-bit particle ids also where nothing draws random numbers per particle, so that
     its particles can be matched with the oracle's one by one."""
     from nanokappa_amd.engine import Engine
@@ -313,7 +351,7 @@ def make_engine(ct, pos, mode, occ, counter, seed, interp=1, T0=298.0, emit_scal
     if ct['rough'] is not None:
         r = ct['rough']
         eng.set_rough(r['facets'], r['specularity'], r['true_spec'], r['spec_map'], r['roulette'], degen_j2=r.get('degen_j2'))
-    eng.set_params(dt=1.0, particle_density=ct['particle_density'], flux_every=flux_every, contains_every=contains_every,
+    eng.set_params(dt=dt, particle_density=ct['particle_density'], flux_every=flux_every, contains_every=contains_every,
                    track_ids=track_ids)
     if comm is not None:                      # (unique id, rank, nranks), before the first step
         eng.comm_init(*comm)
