@@ -453,6 +453,12 @@ const char *nk_group_last_error(const nk_group *g);   /* g may be NULL: error of
 int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
                      double *xc, double *tc, int32_t *fc);                       /* Mesh.py:806-856 */
 int nk_classify(nk_ctx *ctx, int64_t n, const double *x, int32_t *id);           /* Geometry.py:1212 */
+/* The box store's wall functions (nk_device.h) on n rays, with the context's walls, tol and dt; NK_ERR_ARG unless nk_set_mesh
+ * found a box.  which: 0 nk_box_out (t = 1.0 / 0.0, facet = -1; x is the end-of-step position), 1 nk_box_first_hit (t = the
+ * crossing time in timesteps from the end of the step, negative; its facet), 2 nk_box_next_hit (t = time to the next wall,
+ * its facet; inf, -1 on a miss).  Needs no particle store. */
+int nk_box_hit(nk_ctx *ctx, int32_t which, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
+               double *t /* [n] */, int32_t *facet /* [n] */);
 int nk_eval(nk_ctx *ctx, int32_t what, int64_t n, const double *a, const int32_t *mode, double *out);
 /* what: 0 occupation(T=a[i], omega[mode[i]]) Phonon.py:338; 1 lifetime(T=a[i], mode[i]) Phonon.py:336;
  *       2 T(E=a[i]) Phonon.py:387; 3 E(T=a[i]) Phonon.py:390; 4 per-particle T at x=a[3i..] Population.py:696;

@@ -3525,6 +3525,18 @@ int nk_classify(nk_ctx *ctx, int64_t n, const double *x, int32_t *id) {
     NK_HIP(did.get(id, n));
     return NK_OK;
 }
+int nk_box_hit(nk_ctx *ctx, int32_t which, int64_t n, const double *x, const double *v, double *t, int32_t *facet) {
+    NK_ARG(ctx && ctx->have_mesh && n > 0 && x && v && t && facet && which >= 0 && which <= 2, "nk_box_hit: bad arguments");
+    NK_ARG(ctx->mesh_box, "nk_box_hit: the mesh is not a box (six axis-aligned walls, one facet each)");
+    NK_HIP(hipSetDevice(ctx->device));
+    NK_BUF(double, dx, x, n * 3); NK_BUF(double, dv, v, n * 3);
+    NK_BUF(double, dt, nullptr, n); NK_BUF(int32_t, df, nullptr, n);
+    k_tap_box_hit<<<(int)((n + NK_WG - 1) / NK_WG), NK_WG, 0, ctx->stream>>>(ctx->d, which, n, dx.p, dv.p, dt.p, df.p);
+    NK_HIP(hipGetLastError());
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    NK_HIP(dt.get(t, n)); NK_HIP(df.get(facet, n));
+    return NK_OK;
+}
 int nk_eval(nk_ctx *ctx, int32_t what, int64_t n, const double *a, const int32_t *mode, double *out) {
     NK_ARG(ctx && ctx->have_material && n > 0 && a && out && what >= 0 && what <= 8, "nk_eval: bad arguments");
     NK_ARG((what > 1 && what != 8) || mode, "nk_eval: mode required");

@@ -2388,6 +2388,20 @@ NK_KERNEL_LINKAGE __global__ __launch_bounds__(NK_WG) void k_tap_classify(NkDev 
     int64_t i = (int64_t)blockIdx.x * NK_WG + threadIdx.x;
     if (i < n) id[i] = nk_classify(d, L.tb, x[3 * i], x[3 * i + 1], x[3 * i + 2]);
 }
+// the box store's wall functions on one ray each: which = 0 nk_box_out, 1 nk_box_first_hit, 2 nk_box_next_hit
+NK_KERNEL_LINKAGE __global__ __launch_bounds__(NK_WG) void k_tap_box_hit(NkDev d, int which, int64_t n, const double *x, const double *v,
+                                                       double *t, int32_t *facet) {
+    NkBoxWalls bw;
+    bw.load(d);
+    int64_t i = (int64_t)blockIdx.x * NK_WG + threadIdx.x;
+    if (i >= n) return;
+    const double px = x[3 * i], py = x[3 * i + 1], pz = x[3 * i + 2], vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
+    double to = 0.0; int fo = -1;
+    if (which == 0) to = nk_box_out(bw, px, py, pz, vx, vy, vz) ? 1.0 : 0.0;
+    else if (which == 1) nk_box_first_hit(bw, d.inv_dt, px, py, pz, vx, vy, vz, to, fo);
+    else nk_box_next_hit(bw, d.tol, px, py, pz, vx, vy, vz, to, fo);
+    t[i] = to; facet[i] = fo;
+}
 NK_KERNEL_LINKAGE __global__ __launch_bounds__(NK_WG) void k_tap_eval(NkDev d, int what, int64_t n, const double *a, const int32_t *mode,
                                                     double *out) {
     extern __shared__ __align__(16) unsigned char smem[];

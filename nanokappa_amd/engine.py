@@ -84,7 +84,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_reservoirs', 'nk_set_rough', 'nk_set_params', 'nk_reserve', 'nk_upload_particles',
            'nk_init_boundaries', 'nk_step', 'nk_download_particles', 'nk_get_subvol_temperature',
            'nk_set_subvol_temperature', 'nk_get_step', 'nk_get_timing', 'nk_comm_unique_id', 'nk_comm_init',
-           'nk_find_boundary', 'nk_classify', 'nk_eval', 'nk_mode_segments', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
+           'nk_find_boundary', 'nk_classify', 'nk_box_hit', 'nk_eval', 'nk_mode_segments', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
            'nk_specular_begin', 'nk_specular_pairs', 'nk_specular_end', 'nk_rough_begin', 'nk_rough_pairs', 'nk_rough_finish',
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
@@ -177,6 +177,7 @@ def load_library():
     L.nk_comm_allreduce.argtypes = [C.c_void_p, c_dp, C.c_int64]
     L.nk_find_boundary.argtypes = [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, c_ip]
     L.nk_classify.argtypes = [C.c_void_p, C.c_int64, c_dp, c_ip]
+    L.nk_box_hit.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_dp, c_dp, c_dp, c_ip]
     L.nk_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_dp, c_ip, c_dp]
     L.nk_mode_segments.argtypes = [C.c_void_p, c_ip, C.POINTER(C.c_int32)]
     L.nk_reflect.argtypes = [C.c_void_p, C.c_int64, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp, c_dp]
@@ -837,6 +838,15 @@ class Engine(object):
         out = np.zeros(x.shape[0], dtype=np.int32)
         self._ck(self.L.nk_classify(self.h, x.shape[0], _p(x), _p(out, c_ip)), 'nk_classify')
         return out
+
+    def box_hit(self, which, x, v):
+        """The box store's wall functions on rays (x, v): which = 0 nk_box_out -> (1.0 / 0.0, -1), 1 nk_box_first_hit -> (n_timesteps,
+        facet), 2 nk_box_next_hit -> (t, facet).  Only on a mesh that nk_set_mesh found to be a box."""
+        x, v = _d(x), _d(v)
+        n = x.shape[0]
+        t, f = np.zeros(n), np.zeros(n, dtype=np.int32)
+        self._ck(self.L.nk_box_hit(self.h, int(which), n, _p(x), _p(v), _p(t), _p(f, c_ip)), 'nk_box_hit')
+        return t, f
 
     def eval(self, what, a, mode=None):
         code = {'occupation': 0, 'lifetime': 1, 'T_of_E': 2, 'E_of_T': 3, 'interp_T': 4, 'exp': 5, 'exp_small': 6, 'rcp': 7,
