@@ -408,6 +408,59 @@ typedef struct {
 } nk_modes_report;
 int nk_modes_info(nk_ctx *ctx, nk_modes_report *out);
 
+/* Free-path sampling: what conductivity the geometry and the material alone allow, read off ray casts before a single step.
+ * For every mode of the list n_samples rays start uniformly in the solid and fly along the mode's group velocity, W = 1:
+ * per cast (the general cast of the mesh's geometry mode), with tc the time to the hit and a = tc / tau: g = -expm1(-a),
+ * D += W tau g v, T += W tau g, p_int += W g, W *= exp(-a), hits += W; a miss takes g = 1 and ends the ray.  At a hit the
+ * facet decides: 'T' / 'F' p_res += W, end; 'P' go on from the hit point + the facet's translation; 'R' draws (r0, r1): specular
+ * iff true_spec && r0 <= specularity -- go on from the hit point in mode spec_map (its degenerate partner when degen_j2 names one
+ * and r1 >= 0.5) -- else diffuse: p_wall += W, end.  A ray also ends when W < w_min or after max_segments hits (its W goes to
+ * w_left).  A mode with v = 0 or tau <= 0 takes no cast (p_int = its whole weight).  Per mode p_res + p_wall + w_left + p_int =
+ * n_samples.  An ESTIMATE of the conductivity (kappa_ab = sum_m C_m v_a D_b / (n QV), the host's part): exact (Fuchs-Sondheimer)
+ * where the walls that end the flights are parallel to the transport direction, an approximation where reservoirs end them along
+ * it.  The pass has device buffers of its own for the length of the call and touches neither the particle store nor the step
+ * counter: it may be called at any point between nk_step calls, with or without particles.  No atomics: a mode's row is the same
+ * bits whatever the other modes of the list. */
+typedef struct {
+    int32_t n_modes;             /* entries of `modes`; ignored when it is NULL */
+    const int32_t *modes;        /* [n_modes] global mode indices q*J + j, or NULL: all Q*J modes, in order */
+    int32_t n_samples;           /* rays per mode */
+    int32_t max_segments;        /* hits after which a ray is cut off; 0 = 65536 */
+    double w_min;                /* weight below which a ray ends; 0 = 2^-40 */
+    const double *tau;           /* [Q*J] lifetimes (ps) at the temperature of the estimate */
+    const double *x0;            /* [rays*3] start points, ray = list index * n_samples + sample, or NULL: drawn on the device */
+    uint64_t seed;               /* Philox key; 0 = the context's */
+} nk_free_path_args;
+typedef struct {                 /* per mode of the list; any pointer may be NULL */
+    double *D;                   /* [n*3] sum of the rays' displacements (angstrom) */
+    double *D2;                  /* [n*3] sum of their squares, per component */
+    double *T;                   /* [n]   sum of the flight times (ps) */
+    double *hits;                /* [n]   sum over the hits of the weight that arrived */
+    double *p_res, *p_wall;      /* [n]   weight absorbed by reservoirs / scattered diffusely by walls */
+    double *w_left;              /* [n]   weight of the rays cut off (w_min, max_segments) */
+    double *p_int;               /* [n]   weight scattered intrinsically: sum of T / tau per segment */
+} nk_free_path_modes;
+typedef struct {                 /* per ray (tests and small calls); any pointer may be NULL */
+    double *D;                   /* [rays*3] */
+    double *T;                   /* [rays] */
+    int32_t *segments;           /* [rays] casts of the ray */
+    int32_t *end;                /* [rays] 0 weight exhausted, 1 reservoir, 2 diffuse wall, 3 miss, 4 cap */
+    double *x0;                  /* [rays*3] the start points used */
+} nk_free_path_rays;
+typedef struct {
+    int64_t rays, casts, missed, capped;
+    int32_t geometry_mode;       /* 1 planes and faces in LDS, 2 tables in global memory (face tree) */
+    int32_t calls;               /* nk_free_paths calls on this context so far */
+    int64_t bytes;               /* device memory the last call allocated (and freed) */
+    double seconds;              /* device time of the kernel, from HIP events */
+} nk_free_path_report;
+/* NK_ERR_ARG, with a text that names the cause: no material or mesh, 'R' facets without rough tables (nk_set_rough /
+ * nk_rough_finish), no x0 on a mesh that was set without its volume tables, n_samples <= 0, a mode out of range, tau NULL. */
+int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *args, const nk_free_path_modes *modes, const nk_free_path_rays *rays,
+                  nk_free_path_report *report);
+/* The report of the last call; all zero on a context that never made one (nothing was launched or allocated). */
+int nk_free_paths_info(nk_ctx *ctx, nk_free_path_report *out);
+
 /* Replica groups: R contexts that hold the same problem under different seeds (the runs behind an error bar) are stepped by
  * shared launches -- per step ONE sweep and ONE tail launch for all of them instead of R of each, and one wait per call.  A
  * workgroup of the shared launch finds its member and runs that member's step exactly as nk_step would: the rows and the

@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid` and `--mode_tally`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally` and `--free_path`."""
 import argparse
 import os
 import sys
@@ -69,6 +69,12 @@ def initialise_parser(debug_flag=False):
       help='[every]: tally energy and particle count per (subvolume, mode) every `every` steps (default 100, a multiple of '
            'n_dt_to_conv = 10) on the GPU over the convergence window, and write mode_tally.npz and the conductivity '
            'accumulated over the mean free path, k_accumulation.txt; 0 = off (the default)')
+    a('--free_path', default=[], type=str, nargs='*',
+      help='N [T] [max_segments]: before the first step, estimate the conductivity the geometry and the material alone allow by '
+           'free-path sampling on the GPU -- N rays per mode from start points uniform in the solid, flown along the group '
+           'velocity until a boundary ends them, weighed with the lifetimes at T (default: the mean reservoir temperature) -- '
+           'and write k_free_path.txt (tensor with its standard error, bulk value, accumulation over the mean free path) and '
+           'free_path.npz (per-mode arrays); off by default')
     a('--replicas', default=[1], type=int, nargs=1,
       help='R: run the same problem under the seeds seed, seed + 1, ..., seed + R - 1 (an error bar on the conductivity); '
            'every replica writes its files to replica_<k> of the results folder, ensemble.txt holds the mean, the standard '

@@ -22,6 +22,7 @@
 #include "nk_field.h"
 #include "nk_modes.h"
 #include "nk_group.h"
+#include "nk_freepath.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -143,6 +144,8 @@ struct nk_ctx {
     // mode-resolved tally (nk_set_modes, k_modes; nk_modes.hip): off by default -- then nothing is launched or allocated
     NkModesHost modes;
     double res_T_max = 0.0;              // highest reservoir temperature (nk_set_reservoirs): bounds the field's terms
+    // free-path sampling (nk_free_paths, k_free_paths; nk_freepath.hip): the last call's report -- nothing is kept on the device
+    nk_free_path_report fp_last = {};
 };
 
 #define NK_HIP(call)                                                                                   \
@@ -3876,5 +3879,106 @@ int nk_build_enter_prob(nk_ctx *ctx, int32_t R, const double *normal_in, const d
     NK_HIP(hipGetLastError());
     NK_HIP(hipStreamSynchronize(ctx->stream));
     NK_HIP(dout.get(out, (int64_t)n));
+    return NK_OK;
+}
+
+// ------------------------------------------------------------------------------------- free-path sampling
+// k_free_paths (nk_freepath.hip) on buffers of this call alone: the particle store, its counters, the step counter and the
+// emission bookkeeping are neither read nor written.
+int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_path_modes *pm, const nk_free_path_rays *pr, nk_free_path_report *rep) {
+    if (rep) memset(rep, 0, sizeof(*rep));
+    NK_ARG(ctx && a, "nk_free_paths: NULL argument");
+    NK_ARG(ctx->have_material, "nk_free_paths: no material (nk_set_material first)");
+    NK_ARG(ctx->have_mesh, "nk_free_paths: no mesh (nk_set_mesh first)");
+    NkDev &d = ctx->d;
+    NK_ARG(a->tau, "nk_free_paths: tau is NULL (the lifetimes of all Q*J modes at the temperature of the estimate)");
+    NK_ARG(a->n_samples > 0, "nk_free_paths: n_samples = " + std::to_string(a->n_samples) + " must be positive");
+    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, "nk_free_paths: max_segments and w_min must not be negative");
+    const int64_t nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
+    NK_ARG(nlist >= 0, "nk_free_paths: n_modes must not be negative");
+    if (a->modes)
+        for (int64_t i = 0; i < nlist; ++i)
+            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, "nk_free_paths: mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
+                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
+    for (int fc = 0; fc < d.Fc; ++fc)
+        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
+               "nk_free_paths: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
+    NK_ARG(a->x0 || d.nS > 0, "nk_free_paths: no start points (x0) and the mesh was set without its volume tables (simplices)");
+    const int64_t rays = nlist * (int64_t)a->n_samples;
+    NK_ARG(rays < (1ll << 31), "nk_free_paths: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    NK_HIP(hipSetDevice(ctx->device));
+    const bool want_rays = pr && (pr->D || pr->T || pr->segments || pr->end || pr->x0);
+    NK_BUF(int32_t, dmodes, a->modes, a->modes ? nlist : 0);
+    NK_BUF(double, dtau, a->tau, d.M);
+    NK_BUF(double, dx0, a->x0, a->x0 ? rays * 3 : 0);
+    NK_BUF(double, drows, nullptr, nlist * NK_FP_ROW);
+    NK_BUF(unsigned long long, dcnt, nullptr, nlist * NK_FP_CNT);
+    NK_BUF(double, drD, nullptr, (want_rays && pr->D) ? rays * 3 : 0);
+    NK_BUF(double, drT, nullptr, (want_rays && pr->T) ? rays : 0);
+    NK_BUF(double, drx, nullptr, (want_rays && pr->x0) ? rays * 3 : 0);
+    NK_BUF(int32_t, drs, nullptr, (want_rays && pr->segments) ? rays : 0);
+    NK_BUF(int32_t, dre, nullptr, (want_rays && pr->end) ? rays : 0);
+    NkFreeDev f;
+    f.modes = a->modes ? dmodes.p : nullptr;
+    f.nlist = (int32_t)nlist; f.n = a->n_samples;
+    f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
+    f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
+    f.tau = dtau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? dx0.p : nullptr;
+    f.seed = a->seed ? a->seed : d.seed;
+    f.rows = drows.p; f.counts = dcnt.p;
+    f.ray_D = (want_rays && pr->D) ? drD.p : nullptr; f.ray_T = (want_rays && pr->T) ? drT.p : nullptr;
+    f.ray_x0 = (want_rays && pr->x0) ? drx.p : nullptr;
+    f.ray_seg = (want_rays && pr->segments) ? drs.p : nullptr; f.ray_end = (want_rays && pr->end) ? dre.p : nullptr;
+    nk_free_path_report r;
+    memset(&r, 0, sizeof(r));
+    r.rays = rays;
+    r.geometry_mode = nk_geom_mode(ctx);
+    r.calls = ctx->fp_last.calls + 1;
+    r.bytes = (a->modes ? nlist * 4 : 0) + (int64_t)d.M * 8 + (a->x0 ? rays * 24 : 0) + nlist * (NK_FP_ROW + NK_FP_CNT) * 8 +
+              (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) + (f.ray_x0 ? rays * 24 : 0) + (f.ray_seg ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
+    if (e == hipSuccess) e = nk_free_paths_launch(d, f, r.geometry_mode, nk_lds(ctx, true), ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    NK_HIP(e);
+    r.seconds = 1e-3 * (double)ms;
+    std::vector<double> rows((size_t)nlist * NK_FP_ROW);
+    std::vector<unsigned long long> cnt((size_t)nlist * NK_FP_CNT);
+    NK_HIP(drows.get(rows.data(), nlist * NK_FP_ROW));
+    NK_HIP(dcnt.get(cnt.data(), nlist * NK_FP_CNT));
+    for (int64_t i = 0; i < nlist; ++i) {
+        const double *w = &rows[(size_t)i * NK_FP_ROW];
+        if (pm) {
+            for (int c = 0; c < 3; ++c) { if (pm->D) pm->D[3 * i + c] = w[c]; if (pm->D2) pm->D2[3 * i + c] = w[3 + c]; }
+            if (pm->T) pm->T[i] = w[6];
+            if (pm->hits) pm->hits[i] = w[7];
+            if (pm->p_res) pm->p_res[i] = w[8];
+            if (pm->p_wall) pm->p_wall[i] = w[9];
+            if (pm->w_left) pm->w_left[i] = w[10];
+            if (pm->p_int) pm->p_int[i] = w[11];
+        }
+        r.casts += (int64_t)cnt[(size_t)i * NK_FP_CNT]; r.missed += (int64_t)cnt[(size_t)i * NK_FP_CNT + 1]; r.capped += (int64_t)cnt[(size_t)i * NK_FP_CNT + 2];
+    }
+    if (want_rays) {
+        if (pr->D) NK_HIP(drD.get(pr->D, rays * 3));
+        if (pr->T) NK_HIP(drT.get(pr->T, rays));
+        if (pr->x0) NK_HIP(drx.get(pr->x0, rays * 3));
+        if (pr->segments) NK_HIP(drs.get(pr->segments, rays));
+        if (pr->end) NK_HIP(dre.get(pr->end, rays));
+    }
+    ctx->fp_last = r;
+    if (rep) *rep = r;
+    return NK_OK;
+}
+int nk_free_paths_info(nk_ctx *ctx, nk_free_path_report *out) {
+    NK_ARG(ctx && out, "nk_free_paths_info: NULL argument");
+    *out = ctx->fp_last;
     return NK_OK;
 }

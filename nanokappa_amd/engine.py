@@ -92,7 +92,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_field_groups', 'nk_get_field_groups', 'nk_tally_field_groups_state', 'nk_field_groups_info',
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
-           'nk_cell_solid_volume', 'nk_solid_last_error']
+           'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -121,6 +121,25 @@ class nk_modes_report(C.Structure):
 
 class nk_solid_report(C.Structure):
     _fields_ = [('ncells', C.c_int64), ('pairs', C.c_int64), ('k_A', C.c_int32), ('k_P', C.c_int32), ('seconds', C.c_double)]
+
+
+class nk_free_path_args(C.Structure):
+    _fields_ = [('n_modes', C.c_int32), ('modes', c_ip), ('n_samples', C.c_int32), ('max_segments', C.c_int32),
+                ('w_min', C.c_double), ('tau', c_dp), ('x0', c_dp), ('seed', C.c_uint64)]
+
+
+class nk_free_path_modes(C.Structure):
+    _fields_ = [('D', c_dp), ('D2', c_dp), ('T', c_dp), ('hits', c_dp), ('p_res', c_dp), ('p_wall', c_dp), ('w_left', c_dp),
+                ('p_int', c_dp)]
+
+
+class nk_free_path_rays(C.Structure):
+    _fields_ = [('D', c_dp), ('T', c_dp), ('segments', c_ip), ('end', c_ip), ('x0', c_dp)]
+
+
+class nk_free_path_report(C.Structure):
+    _fields_ = [('rays', C.c_int64), ('casts', C.c_int64), ('missed', C.c_int64), ('capped', C.c_int64),
+                ('geometry_mode', C.c_int32), ('calls', C.c_int32), ('bytes', C.c_int64), ('seconds', C.c_double)]
 
 
 class nk_group_report(C.Structure):
@@ -220,6 +239,9 @@ def load_library():
     L.nk_cell_solid_volume.argtypes = [C.c_int, C.c_int64, c_dp, c_dp, c_dp, c_ip, c_dp, C.POINTER(nk_solid_report)]
     L.nk_solid_last_error.restype = C.c_char_p
     L.nk_solid_last_error.argtypes = []
+    L.nk_free_paths.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.POINTER(nk_free_path_modes), C.POINTER(nk_free_path_rays),
+                                C.POINTER(nk_free_path_report)]
+    L.nk_free_paths_info.argtypes = [C.c_void_p, C.POINTER(nk_free_path_report)]
     _lib = L
     return L
 
@@ -351,6 +373,7 @@ class Engine(object):
         self._ck(self.L.nk_set_material(self.h, C.byref(m)), 'nk_set_material')
         self.J = int(m.J)
         self.M = int(m.Q * m.J)
+        self._vg = vg.reshape(-1, 3).copy()            # (free_paths: the default mode list)
 
     def set_mesh(self, g):
         """g: mapping with the reference's Mesh/Geometry attribute names (face_normals, face_k, face_bounds,
@@ -679,6 +702,60 @@ class Engine(object):
         self._ck(self.L.nk_tally_modes_state(self.h, N.ctypes.data_as(C.POINTER(C.c_int64)), E.ctypes.data_as(C.POINTER(C.c_int64))), 'nk_tally_modes_state')
         kE = self.modes_info()['k_E']
         return dict(N_raw=N, E_raw=E, k_E=kE, N=N.astype(np.float64), E=np.ldexp(E.astype(np.float64), -kE))
+
+    # ------------------------------------------------------- free-path sampling
+    @staticmethod
+    def _free_path_report(r):
+        return dict(rays=int(r.rays), casts=int(r.casts), missed=int(r.missed), capped=int(r.capped),
+                    geometry_mode=int(r.geometry_mode), calls=int(r.calls), bytes=int(r.bytes), seconds=float(r.seconds))
+
+    def free_paths(self, tau, n=64, modes=None, max_segments=0, w_min=0.0, x0=None, seed=0, rays=False):
+        """Free-path sampling (nk_free_paths; k_free_paths): n rays for every mode of `modes` (global indices q*J + j; None =
+        every mode with |v| > 0 and tau > 0; 'all' = all Q*J modes), flown along the mode's group velocity until a boundary or the lifetime tau [Q*J] ends them.  x0
+        [len(modes), n, 3]: the start points (None: drawn uniformly in the solid on the device); seed 0 = the engine's;
+        max_segments 0 = 65536, w_min 0 = 2^-40.  Returns a dict: modes, n, the per-mode sums D, D2 [L, 3], T, hits, p_res,
+        p_wall, w_left, p_int [L], and report (rays, casts, missed, capped, geometry_mode, calls, bytes, seconds); with
+        rays=True also ray_D [L, n, 3], ray_T, ray_segments, ray_end, ray_x0 (end codes: 0 weight exhausted, 1 reservoir,
+        2 diffuse wall, 3 miss, 4 cap).  Touches neither the particles nor the step counter."""
+        a = nk_free_path_args()
+        t = None if tau is None else _d(np.ravel(tau))
+        if t is not None and self.M > 0 and t.shape[0] != self.M:
+            raise NkError('free_paths: tau has %d entries, the material %d modes' % (t.shape[0], self.M))
+        if modes is None and t is not None and self.M > 0:
+            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & (t > 0))[0]
+        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
+        L = self.M if ml is None else int(ml.shape[0])
+        n = int(n)
+        xs = None
+        if x0 is not None:
+            xs = _d(x0)
+            if xs.size != L * max(n, 0) * 3:
+                raise NkError('free_paths: x0 needs %d x %d x 3 entries, got %d' % (L, n, xs.size))
+        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
+        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
+        R = L * max(n, 0)
+        out = dict(D=np.zeros((L, 3)), D2=np.zeros((L, 3)), T=np.zeros(L), hits=np.zeros(L), p_res=np.zeros(L), p_wall=np.zeros(L),
+                   w_left=np.zeros(L), p_int=np.zeros(L))
+        pm = nk_free_path_modes()
+        for k in out:
+            setattr(pm, k, _p(out[k]))
+        pr = nk_free_path_rays()
+        if rays:
+            ro = dict(ray_D=np.zeros((L, n, 3)), ray_T=np.zeros((L, n)), ray_segments=np.zeros((L, n), dtype=np.int32),
+                      ray_end=np.zeros((L, n), dtype=np.int32), ray_x0=np.zeros((L, n, 3)))
+            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
+            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
+            out.update(ro)
+        rep = nk_free_path_report()
+        self._ck(self.L.nk_free_paths(self.h, C.byref(a), C.byref(pm), C.byref(pr) if rays else None, C.byref(rep)), 'nk_free_paths')
+        out.update(modes=(np.arange(self.M, dtype=np.int32) if ml is None else ml.copy()), n=n, report=self._free_path_report(rep))
+        return out
+
+    def free_paths_info(self):
+        """The report of the last free_paths call on this engine; all zero (calls = 0, bytes = 0) when there was none."""
+        rep = nk_free_path_report()
+        self._ck(self.L.nk_free_paths_info(self.h, C.byref(rep)), 'nk_free_paths_info')
+        return self._free_path_report(rep)
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

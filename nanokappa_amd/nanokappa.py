@@ -37,6 +37,8 @@ def run_replicas(args, geo, phonons, replicas, start, max_time):
 
 def main(argv=None):
     args = read_args(False, argv)
+    from .free_path import free_path_option
+    fp_n, fp_T, fp_segments = free_path_option(getattr(args, 'free_path', None))     # (refused here, before anything is set up)
     args = generate_results_folder(args)
     out = None
     # nanokappa.py:34-36 compares the parsed value with 'file'; an explicit `--output file` arrives as the list ['file'] and
@@ -69,6 +71,13 @@ def main(argv=None):
             out.close()
         return ens
     pop = Population(args, geo, phonons)
+    if fp_n > 0:                               # --free_path N [T] [max_segments]: after the set-up, before the first step
+        print('Free-path sampling: %d rays per mode...' % fp_n)
+        fp = pop.free_paths(n=fp_n, T=fp_T, max_segments=fp_segments)
+        if fp is not None:
+            a = fp['axis']
+            print('  T = %.2f K: kappa_%s%s = %.4f +- %.4f W/m K (an estimate), bulk %.4f W/m K; %d rays missed, %d cut off' %
+                  (fp['T'], 'xyz'[a], 'xyz'[a], fp['kappa'][a, a], fp['kappa_se'][a, a], fp['kappa_bulk'][a, a], fp['missed'], fp['capped']))
     flag = True
     while flag:
         # batches end on the 100-step bookkeeping boundary, so stop criteria are checked as often as the

@@ -24,6 +24,7 @@ from . import spectral as SP
 from . import field as FD
 from . import field_groups as FG
 from . import modes as MD
+from . import free_path as FP
 from .engine import Engine
 from .sharding import shard_range
 
@@ -525,6 +526,49 @@ class Population(Constants):
             a = self.kappa_accumulation(by, dist=d)
             MD.write_k_accumulation(MD.k_accumulation_path(folder, by), a['grid'], a['k'], con, by=by, steps=d['step'])
         return MD.write_mode_tally(MD.mode_tally_path(folder), d['N'], d['E'], d['samples'], d['step'], self._ph.omega, self._ph.group_vel)
+
+    # ----------------------------------------------------------------------- free-path sampling
+    def _mean_reservoir_T(self):
+        """The temperature of the 'mfp' groups: the mean reservoir temperature; without reservoirs the reference temperature,
+        or the mean subvolume temperature where that is 'local'."""
+        rt = np.asarray(getattr(self, 'res_facet_temperature', np.zeros(0)), dtype=float)
+        rt = rt[np.isfinite(rt)]
+        if rt.size:
+            return float(rt.mean())
+        if self.T_reference == 'local':
+            return float(np.mean(self.subvol_temperature))
+        return float(self.T_reference)
+
+    def free_paths(self, n=FP.N_DEFAULT, T=None, modes=None, max_segments=FP.MAX_SEGMENTS_DEFAULT, w_min=FP.W_MIN_DEFAULT, x0=None,
+                   seed=0, axis=None, write=True):
+        """The conductivity the geometry and the material alone allow, by free-path sampling on the GPU (Engine.free_paths):
+        n rays per mode of `modes` (default: every mode with |v| > 0 and tau > 0) with the lifetimes of Phonon.lifetime_function
+        at T (default: the mean reservoir temperature, the rule of the 'mfp' groups).  Returns free_path.summarise()'s dict
+        (kappa [3, 3] with its standard error, kappa_bulk, suppression, accumulation over the mean free path along `axis`,
+        default the slice axis, ...) and, with a results folder, writes k_free_path.txt and free_path.npz.  An estimate (see
+        free_path.py).  May be called at any point of a run: particles and step counter are not touched.  With several ranks
+        rank 0 computes and writes; the others return None."""
+        if self.rank != 0:
+            return None
+        ph = self._ph
+        T = self._mean_reservoir_T() if T is None else float(T)
+        tau = FP.lifetimes(ph, T)
+        if modes is None:
+            modes = FP.default_modes(ph.group_vel, tau)
+        if axis is None:
+            axis = int(getattr(self, 'slice_axis', 0) or 0)
+        res = self.engine.free_paths(tau, n=int(n), modes=modes, max_segments=int(max_segments), w_min=float(w_min), x0=x0, seed=int(seed))
+        s = FP.summarise(res, ph.omega, ph.group_vel, tau, ph.number_of_qpoints * ph.volume_unitcell, T, axis=axis, hbar=self.hbar,
+                         kb=self.kb)
+        self.free_path_last = s
+        if write and self.results_folder_name:
+            FP.write_k_free_path(FP.k_free_path_path(self.results_folder_name), s)
+            FP.write_free_path_npz(FP.free_path_npz_path(self.results_folder_name), s)
+        return s
+
+    def free_path_report(self):
+        """The engine's report of its last free-path call; calls = 0 and bytes = 0 when there was none."""
+        return self.engine.free_paths_info()
 
     # ----------------------------------------------------------------------------------- setup
     def _shard(self, n):
