@@ -461,6 +461,38 @@ int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *args, const nk_free_path
 /* The report of the last call; all zero on a context that never made one (nothing was launched or allocated). */
 int nk_free_paths_info(nk_ctx *ctx, nk_free_path_report *out);
 
+/* Free-path sweeps: the rays of nk_free_paths weighed with K lifetime tables at once.  The path of a ray -- start point, facets,
+ * translations, specular / diffuse draws, the modes it is reflected into -- does not depend on the lifetimes, so every ray is
+ * cast once per segment and every column c keeps weights of its own {W, D, T}: while it is alive it takes the statements of
+ * nk_free_paths with tau = column c; it starts dead where the start mode has v = 0 or tau_c <= 0, and ends by the rules above
+ * (its own W against w_min; the hit count against max_segments is the ray's).  The ray flies while any column is alive.
+ * Column c of the result equals nk_free_paths called with tau = row c of `tau` on the same list, n_samples, x0 or seed,
+ * max_segments and w_min, bit for bit: per-mode sums, per-ray outputs and counts; it depends neither on the other modes of the
+ * list nor on the other columns of the call.  args->tau is [n_columns][Q*J] (row c = column c); every array of `modes` and of
+ * `rays` has a leading column axis ([n_columns][n*3], [n_columns][rays], ...) except rays->x0 [rays*3], which is the ray's.
+ * Up to `tile` columns share a cast; a call with more is flown in ceil(n_columns / tile) launches that repeat the casts.
+ * A geometry scaled by s with unchanged roughness is the same flight with lifetimes tau / s and displacements s D; a temperature
+ * enters through tau(T) alone: the host builds both sweeps on this call.  Buffers of the call alone, as nk_free_paths. */
+#define NK_FREE_PATH_MAX_COLUMNS 32
+typedef struct {
+    int64_t rays;                /* rays flown (per tile of columns) */
+    int64_t casts_shared;        /* casts made: = casts[0] for one column, never more than the sum of the columns' */
+    int64_t casts[NK_FREE_PATH_MAX_COLUMNS];     /* per column: casts made while it was alive (nk_free_paths' `casts`) */
+    int64_t missed[NK_FREE_PATH_MAX_COLUMNS], capped[NK_FREE_PATH_MAX_COLUMNS];
+    int32_t n_columns;
+    int32_t tile;                /* columns that share a cast */
+    int32_t launches;            /* kernel launches of the call: tiles of columns */
+    int32_t geometry_mode;       /* as nk_free_path_report */
+    int32_t calls;               /* nk_free_paths_columns calls on this context so far */
+    int32_t pad_;
+    int64_t bytes;               /* device memory the call allocated (and freed) */
+    double seconds;              /* device time of the launches, from HIP events */
+} nk_free_path_columns_report;
+/* NK_ERR_ARG, with a text that names the cause: n_columns outside 1 .. NK_FREE_PATH_MAX_COLUMNS, and every refusal of
+ * nk_free_paths, in its words; nothing is launched or allocated then and the report is all zero. */
+int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *args, int32_t n_columns, const nk_free_path_modes *modes,
+                          const nk_free_path_rays *rays, nk_free_path_columns_report *report);
+
 /* Replica groups: R contexts that hold the same problem under different seeds (the runs behind an error bar) are stepped by
  * shared launches -- per step ONE sweep and ONE tail launch for all of them instead of R of each, and one wait per call.  A
  * workgroup of the shared launch finds its member and runs that member's step exactly as nk_step would: the rows and the

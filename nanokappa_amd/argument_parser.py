@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally` and `--free_path`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path` and `--free_path_sweep`."""
 import argparse
 import os
 import sys
@@ -75,6 +75,12 @@ def initialise_parser(debug_flag=False):
            'velocity until a boundary ends them, weighed with the lifetimes at T (default: the mean reservoir temperature) -- '
            'and write k_free_path.txt (tensor with its standard error, bulk value, accumulation over the mean free path) and '
            'free_path.npz (per-mode arrays); off by default')
+    a('--free_path_sweep', default=[], type=str, nargs='*',
+      help='scale s1 s2 ... | temperature T1 T2 ...: with --free_path N, also weigh the same rays once per value (at most 32) -- '
+           'the structure scaled by s with unchanged roughness, or the structure as it is at the temperature T (K) -- and write '
+           'k_free_path_sweep.txt (one line per value: kappa along the axis, its standard error, the bulk value, their ratio) and '
+           'free_path_sweep.npz (per value the tensors, the per-mode suppression, the accumulation over the mean free path on '
+           'one grid); off by default')
     a('--replicas', default=[1], type=int, nargs=1,
       help='R: run the same problem under the seeds seed, seed + 1, ..., seed + R - 1 (an error bar on the conductivity); '
            'every replica writes its files to replica_<k> of the results folder, ensemble.txt holds the mean, the standard '

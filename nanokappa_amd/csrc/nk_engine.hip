@@ -23,6 +23,7 @@
 #include "nk_modes.h"
 #include "nk_group.h"
 #include "nk_freepath.h"
+#include "nk_freecols.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -146,6 +147,7 @@ struct nk_ctx {
     double res_T_max = 0.0;              // highest reservoir temperature (nk_set_reservoirs): bounds the field's terms
     // free-path sampling (nk_free_paths, k_free_paths; nk_freepath.hip): the last call's report -- nothing is kept on the device
     nk_free_path_report fp_last = {};
+    int32_t fc_calls = 0;        // nk_free_paths_columns calls so far (k_free_columns; nk_freecols.hip)
 };
 
 #define NK_HIP(call)                                                                                   \
@@ -3980,5 +3982,123 @@ int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_path_mo
 int nk_free_paths_info(nk_ctx *ctx, nk_free_path_report *out) {
     NK_ARG(ctx && out, "nk_free_paths_info: NULL argument");
     *out = ctx->fp_last;
+    return NK_OK;
+}
+
+// k_free_columns (nk_freecols.hip): the rays of nk_free_paths cast once and weighed with K lifetime tables.  Buffers of this call
+// alone, as above; a call with more than NK_FC_TILE columns is flown in tiles of that many (one launch each, the casts repeated).
+int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *a, int32_t n_columns, const nk_free_path_modes *pm, const nk_free_path_rays *pr,
+                          nk_free_path_columns_report *rep) {
+    if (rep) memset(rep, 0, sizeof(*rep));
+    NK_ARG(ctx && a, "nk_free_paths_columns: NULL argument");
+    NK_ARG(n_columns >= 1 && n_columns <= NK_FREE_PATH_MAX_COLUMNS, "nk_free_paths_columns: n_columns = " + std::to_string(n_columns) +
+                                                                        " must be 1 .. " + std::to_string(NK_FREE_PATH_MAX_COLUMNS));
+    NK_ARG(ctx->have_material, "nk_free_paths_columns: no material (nk_set_material first)");
+    NK_ARG(ctx->have_mesh, "nk_free_paths_columns: no mesh (nk_set_mesh first)");
+    NkDev &d = ctx->d;
+    NK_ARG(a->tau, "nk_free_paths_columns: tau is NULL (per column the lifetimes of all Q*J modes)");
+    NK_ARG(a->n_samples > 0, "nk_free_paths_columns: n_samples = " + std::to_string(a->n_samples) + " must be positive");
+    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, "nk_free_paths_columns: max_segments and w_min must not be negative");
+    const int64_t nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
+    NK_ARG(nlist >= 0, "nk_free_paths_columns: n_modes must not be negative");
+    if (a->modes)
+        for (int64_t i = 0; i < nlist; ++i)
+            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, "nk_free_paths_columns: mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
+                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
+    for (int fc = 0; fc < d.Fc; ++fc)
+        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
+               "nk_free_paths_columns: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
+    NK_ARG(a->x0 || d.nS > 0, "nk_free_paths_columns: no start points (x0) and the mesh was set without its volume tables (simplices)");
+    const int64_t rays = nlist * (int64_t)a->n_samples;
+    NK_ARG(rays < (1ll << 31), "nk_free_paths_columns: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    NK_HIP(hipSetDevice(ctx->device));
+    const int64_t K = n_columns;
+    const int ntiles = (int)((K + NK_FC_TILE - 1) / NK_FC_TILE);
+    const unsigned grid = nk_free_columns_grid(nlist, a->n_samples);
+    const int64_t nacc = a->n_samples > 64 ? (int64_t)grid * NK_FP_WAVES * (K < NK_FC_TILE ? K : NK_FC_TILE) * NK_FC_ACC * 64 : 0;
+    const bool want_rays = pr && (pr->D || pr->T || pr->segments || pr->end || pr->x0);
+    NK_BUF(int32_t, dmodes, a->modes, a->modes ? nlist : 0);
+    NK_BUF(double, dtau, a->tau, K * d.M);
+    NK_BUF(double, dx0, a->x0, a->x0 ? rays * 3 : 0);
+    NK_BUF(double, drows, nullptr, K * nlist * NK_FP_ROW);
+    NK_BUF(unsigned long long, dcnt, nullptr, K * nlist * NK_FP_CNT);
+    NK_BUF(unsigned long long, dshared, nullptr, (int64_t)ntiles * nlist);
+    NK_BUF(double, dacc, nullptr, nacc);
+    NK_BUF(double, drD, nullptr, (want_rays && pr->D) ? K * rays * 3 : 0);
+    NK_BUF(double, drT, nullptr, (want_rays && pr->T) ? K * rays : 0);
+    NK_BUF(double, drx, nullptr, (want_rays && pr->x0) ? rays * 3 : 0);
+    NK_BUF(int32_t, drs, nullptr, (want_rays && pr->segments) ? K * rays : 0);
+    NK_BUF(int32_t, dre, nullptr, (want_rays && pr->end) ? K * rays : 0);
+    NkFreeColsDev q;
+    NkFreeDev &f = q.f;
+    f.modes = a->modes ? dmodes.p : nullptr;
+    f.nlist = (int32_t)nlist; f.n = a->n_samples;
+    f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
+    f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
+    f.tau = dtau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? dx0.p : nullptr;
+    f.seed = a->seed ? a->seed : d.seed;
+    f.rows = drows.p; f.counts = dcnt.p;
+    f.ray_D = (want_rays && pr->D) ? drD.p : nullptr; f.ray_T = (want_rays && pr->T) ? drT.p : nullptr;
+    f.ray_x0 = (want_rays && pr->x0) ? drx.p : nullptr;
+    f.ray_seg = (want_rays && pr->segments) ? drs.p : nullptr; f.ray_end = (want_rays && pr->end) ? dre.p : nullptr;
+    q.M = d.M; q.rays = rays; q.acc = nacc ? dacc.p : nullptr;
+    nk_free_path_columns_report r;
+    memset(&r, 0, sizeof(r));
+    r.rays = rays;
+    r.n_columns = n_columns; r.tile = NK_FC_TILE; r.launches = nlist > 0 ? ntiles : 0;
+    r.geometry_mode = nk_geom_mode(ctx);
+    r.calls = ctx->fc_calls + 1;
+    r.bytes = (a->modes ? nlist * 4 : 0) + K * (int64_t)d.M * 8 + (a->x0 ? rays * 24 : 0) + K * nlist * (NK_FP_ROW + NK_FP_CNT) * 8 + (int64_t)ntiles * nlist * 8 +
+              nacc * 8 + (f.ray_D ? K * rays * 24 : 0) + (f.ray_T ? K * rays * 8 : 0) + (f.ray_x0 ? rays * 24 : 0) + (f.ray_seg ? K * rays * 4 : 0) +
+              (f.ray_end ? K * rays * 4 : 0);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
+    for (int t = 0; t < ntiles && e == hipSuccess; ++t) {
+        q.c0 = t * NK_FC_TILE;
+        q.kc = (int32_t)(K - q.c0 < NK_FC_TILE ? K - q.c0 : NK_FC_TILE);
+        q.shared = dshared.p + (int64_t)t * nlist;
+        e = nk_free_columns_launch(d, q, r.geometry_mode, nk_lds(ctx, true), grid, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    NK_HIP(e);
+    r.seconds = 1e-3 * (double)ms;
+    std::vector<double> rows((size_t)(K * nlist) * NK_FP_ROW);
+    std::vector<unsigned long long> cnt((size_t)(K * nlist) * NK_FP_CNT), shared((size_t)ntiles * nlist);
+    NK_HIP(drows.get(rows.data(), K * nlist * NK_FP_ROW));
+    NK_HIP(dcnt.get(cnt.data(), K * nlist * NK_FP_CNT));
+    NK_HIP(dshared.get(shared.data(), (int64_t)ntiles * nlist));
+    for (unsigned long long v : shared) r.casts_shared += (int64_t)v;
+    for (int64_t c = 0; c < K; ++c)
+        for (int64_t i = 0; i < nlist; ++i) {
+            const int64_t ci = c * nlist + i;
+            const double *w = &rows[(size_t)ci * NK_FP_ROW];
+            if (pm) {
+                for (int x = 0; x < 3; ++x) { if (pm->D) pm->D[3 * ci + x] = w[x]; if (pm->D2) pm->D2[3 * ci + x] = w[3 + x]; }
+                if (pm->T) pm->T[ci] = w[6];
+                if (pm->hits) pm->hits[ci] = w[7];
+                if (pm->p_res) pm->p_res[ci] = w[8];
+                if (pm->p_wall) pm->p_wall[ci] = w[9];
+                if (pm->w_left) pm->w_left[ci] = w[10];
+                if (pm->p_int) pm->p_int[ci] = w[11];
+            }
+            r.casts[c] += (int64_t)cnt[(size_t)ci * NK_FP_CNT]; r.missed[c] += (int64_t)cnt[(size_t)ci * NK_FP_CNT + 1];
+            r.capped[c] += (int64_t)cnt[(size_t)ci * NK_FP_CNT + 2];
+        }
+    if (want_rays) {
+        if (pr->D) NK_HIP(drD.get(pr->D, K * rays * 3));
+        if (pr->T) NK_HIP(drT.get(pr->T, K * rays));
+        if (pr->x0) NK_HIP(drx.get(pr->x0, rays * 3));
+        if (pr->segments) NK_HIP(drs.get(pr->segments, K * rays));
+        if (pr->end) NK_HIP(dre.get(pr->end, K * rays));
+    }
+    ctx->fc_calls = r.calls;
+    if (rep) *rep = r;
     return NK_OK;
 }

@@ -92,7 +92,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_field_groups', 'nk_get_field_groups', 'nk_tally_field_groups_state', 'nk_field_groups_info',
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
-           'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info']
+           'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info', 'nk_free_paths_columns']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -140,6 +140,16 @@ class nk_free_path_rays(C.Structure):
 class nk_free_path_report(C.Structure):
     _fields_ = [('rays', C.c_int64), ('casts', C.c_int64), ('missed', C.c_int64), ('capped', C.c_int64),
                 ('geometry_mode', C.c_int32), ('calls', C.c_int32), ('bytes', C.c_int64), ('seconds', C.c_double)]
+
+
+FREE_PATH_MAX_COLUMNS = 32   # NK_FREE_PATH_MAX_COLUMNS (include/nanokappa_hip.h)
+
+
+class nk_free_path_columns_report(C.Structure):
+    _fields_ = [('rays', C.c_int64), ('casts_shared', C.c_int64), ('casts', C.c_int64 * FREE_PATH_MAX_COLUMNS),
+                ('missed', C.c_int64 * FREE_PATH_MAX_COLUMNS), ('capped', C.c_int64 * FREE_PATH_MAX_COLUMNS),
+                ('n_columns', C.c_int32), ('tile', C.c_int32), ('launches', C.c_int32), ('geometry_mode', C.c_int32),
+                ('calls', C.c_int32), ('pad_', C.c_int32), ('bytes', C.c_int64), ('seconds', C.c_double)]
 
 
 class nk_group_report(C.Structure):
@@ -242,6 +252,8 @@ def load_library():
     L.nk_free_paths.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.POINTER(nk_free_path_modes), C.POINTER(nk_free_path_rays),
                                 C.POINTER(nk_free_path_report)]
     L.nk_free_paths_info.argtypes = [C.c_void_p, C.POINTER(nk_free_path_report)]
+    L.nk_free_paths_columns.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.c_int32, C.POINTER(nk_free_path_modes),
+                                        C.POINTER(nk_free_path_rays), C.POINTER(nk_free_path_columns_report)]
     _lib = L
     return L
 
@@ -756,6 +768,59 @@ class Engine(object):
         rep = nk_free_path_report()
         self._ck(self.L.nk_free_paths_info(self.h, C.byref(rep)), 'nk_free_paths_info')
         return self._free_path_report(rep)
+
+    def free_path_columns(self, taus, n=64, modes=None, max_segments=0, w_min=0.0, x0=None, seed=0, rays=False):
+        """Free-path sampling with K lifetime columns (nk_free_paths_columns; k_free_columns): the rays of free_paths, cast once
+        and weighed with every row of taus [K, Q*J], 1 <= K <= 32.  Column c of the result is free_paths(taus[c], ...) on the
+        same list bit for bit.  modes None = every mode with |v| > 0 and tau > 0 in at least one column; the other arguments as
+        free_paths.  Returns a dict: modes, n, columns (K), the per-mode sums with a leading column axis (D, D2 [K, L, 3], T,
+        hits, p_res, p_wall, w_left, p_int [K, L]), casts, missed, capped [K] and report (rays, casts_shared -- the casts
+        actually made --, n_columns, tile -- the columns that share a cast; more are flown in tiles that repeat the casts --,
+        launches, geometry_mode, calls, bytes, seconds); with rays=True also ray_D [K, L, n, 3], ray_T, ray_segments, ray_end
+        [K, L, n] and ray_x0 [L, n, 3].  free_sweep.column(res, c) gives column c in the shape of a free_paths result."""
+        a = nk_free_path_args()
+        t = None
+        if taus is not None:
+            t = _d(taus)
+            if t.ndim != 2 or (self.M > 0 and t.shape[1] != self.M):
+                raise NkError('free_path_columns failed (%d): taus must be [K, %d] (a row of lifetimes per column), got shape %s' % (ERR_ARG, self.M, t.shape))
+        K = 0 if t is None else int(t.shape[0])
+        if modes is None and t is not None and self.M > 0 and K > 0:
+            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & (t > 0).any(axis=0))[0]
+        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
+        L = self.M if ml is None else int(ml.shape[0])
+        n = int(n)
+        xs = None
+        if x0 is not None:
+            xs = _d(x0)
+            if xs.size != L * max(n, 0) * 3:
+                raise NkError('free_path_columns failed (%d): x0 needs %d x %d x 3 entries, got %d' % (ERR_ARG, L, n, xs.size))
+        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
+        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
+        Ka = max(min(K, FREE_PATH_MAX_COLUMNS), 0)           # (a refused call writes nothing)
+        out = dict(D=np.zeros((Ka, L, 3)), D2=np.zeros((Ka, L, 3)), T=np.zeros((Ka, L)), hits=np.zeros((Ka, L)), p_res=np.zeros((Ka, L)),
+                   p_wall=np.zeros((Ka, L)), w_left=np.zeros((Ka, L)), p_int=np.zeros((Ka, L)))
+        pm = nk_free_path_modes()
+        for k in out:
+            setattr(pm, k, _p(out[k]))
+        pr = nk_free_path_rays()
+        if rays:
+            nn = max(n, 0)
+            ro = dict(ray_D=np.zeros((Ka, L, nn, 3)), ray_T=np.zeros((Ka, L, nn)), ray_segments=np.zeros((Ka, L, nn), dtype=np.int32),
+                      ray_end=np.zeros((Ka, L, nn), dtype=np.int32), ray_x0=np.zeros((L, nn, 3)))
+            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
+            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
+            out.update(ro)
+        rep = nk_free_path_columns_report()
+        self._ck(self.L.nk_free_paths_columns(self.h, C.byref(a), K if t is not None else 1, C.byref(pm), C.byref(pr) if rays else None, C.byref(rep)),
+                 'nk_free_paths_columns')
+        out.update(modes=(np.arange(self.M, dtype=np.int32) if ml is None else ml.copy()), n=n, columns=K,
+                   casts=np.array(rep.casts[:K], dtype=np.int64), missed=np.array(rep.missed[:K], dtype=np.int64),
+                   capped=np.array(rep.capped[:K], dtype=np.int64),
+                   report=dict(rays=int(rep.rays), casts_shared=int(rep.casts_shared), n_columns=int(rep.n_columns), tile=int(rep.tile),
+                               launches=int(rep.launches), geometry_mode=int(rep.geometry_mode), calls=int(rep.calls),
+                               bytes=int(rep.bytes), seconds=float(rep.seconds)))
+        return out
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

@@ -39,6 +39,8 @@ def main(argv=None):
     args = read_args(False, argv)
     from .free_path import free_path_option
     fp_n, fp_T, fp_segments = free_path_option(getattr(args, 'free_path', None))     # (refused here, before anything is set up)
+    from .free_sweep import sweep_option
+    sw_kind, sw_values = sweep_option(getattr(args, 'free_path_sweep', None), fp_n)
     args = generate_results_folder(args)
     out = None
     # nanokappa.py:34-36 compares the parsed value with 'file'; an explicit `--output file` arrives as the list ['file'] and
@@ -78,6 +80,14 @@ def main(argv=None):
             a = fp['axis']
             print('  T = %.2f K: kappa_%s%s = %.4f +- %.4f W/m K (an estimate), bulk %.4f W/m K; %d rays missed, %d cut off' %
                   (fp['T'], 'xyz'[a], 'xyz'[a], fp['kappa'][a, a], fp['kappa_se'][a, a], fp['kappa_bulk'][a, a], fp['missed'], fp['capped']))
+        if sw_kind is not None:                # --free_path_sweep: the same rays, weighed once per value
+            sw = pop.free_path_sweep(sw_kind, sw_values, n=fp_n, T=fp_T, max_segments=fp_segments)
+            if sw is not None:
+                a = sw['axis']
+                print('  sweep over %s, %d casts for %d columns:' % (sw_kind, sw['report']['casts_shared'], len(sw['columns'])))
+                for c in sw['columns']:
+                    print('    %s %g: kappa_%s%s = %.4f +- %.4f W/m K, bulk %.4f W/m K' %
+                          (sw_kind, c['value'], 'xyz'[a], 'xyz'[a], c['kappa'][a, a], c['kappa_se'][a, a], c['kappa_bulk'][a, a]))
     flag = True
     while flag:
         # batches end on the 100-step bookkeeping boundary, so stop criteria are checked as often as the

@@ -25,6 +25,7 @@ from . import field as FD
 from . import field_groups as FG
 from . import modes as MD
 from . import free_path as FP
+from . import free_sweep as FS
 from .engine import Engine
 from .sharding import shard_range
 
@@ -565,6 +566,33 @@ class Population(Constants):
             FP.write_k_free_path(FP.k_free_path_path(self.results_folder_name), s)
             FP.write_free_path_npz(FP.free_path_npz_path(self.results_folder_name), s)
         return s
+
+    def free_path_sweep(self, kind, values, n=FP.N_DEFAULT, T=None, modes=None, max_segments=FP.MAX_SEGMENTS_DEFAULT, w_min=FP.W_MIN_DEFAULT,
+                        x0=None, seed=0, axis=None, write=True):
+        """The estimate of free_paths over a sweep, from ONE set of casts (Engine.free_path_columns): kind 'scale' -- the
+        structure scaled by every value with unchanged roughness, at T (default: the mean reservoir temperature) -- or
+        'temperature' -- the structure as it is at every value (K).  At most free_sweep.MAX_COLUMNS values.  The other arguments
+        as free_paths; the default list holds every mode that flies and lives in at least one column.  Returns
+        free_sweep.summarise_sweep()'s dict and, with a results folder, writes k_free_path_sweep.txt and free_path_sweep.npz.
+        Particles and step counter are not touched.  With several ranks rank 0 computes and writes; the others return None."""
+        if self.rank != 0:
+            return None
+        ph = self._ph
+        kind, vals = FS.sweep_option([kind] + [float(v) for v in np.ravel(values)], n)
+        T = self._mean_reservoir_T() if T is None else float(T)
+        taus = FS.columns_scale(FP.lifetimes(ph, T), vals) if kind == 'scale' else FS.columns_temperature(ph, vals)
+        if modes is None:
+            modes = FP.default_modes(ph.group_vel, taus.max(axis=0))
+        if axis is None:
+            axis = int(getattr(self, 'slice_axis', 0) or 0)
+        res = self.engine.free_path_columns(taus, n=int(n), modes=modes, max_segments=int(max_segments), w_min=float(w_min), x0=x0, seed=int(seed))
+        sw = FS.summarise_sweep(res, kind, vals, ph.omega, ph.group_vel, taus, ph.number_of_qpoints * ph.volume_unitcell, T, axis=axis,
+                                hbar=self.hbar, kb=self.kb)
+        self.free_path_sweep_last = sw
+        if write and self.results_folder_name:
+            FS.write_k_free_path_sweep(FS.k_free_path_sweep_path(self.results_folder_name), sw)
+            FS.write_free_path_sweep_npz(FS.free_path_sweep_npz_path(self.results_folder_name), sw)
+        return sw
 
     def free_path_report(self):
         """The engine's report of its last free-path call; calls = 0 and bytes = 0 when there was none."""
