@@ -493,6 +493,53 @@ typedef struct {
 int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *args, int32_t n_columns, const nk_free_path_modes *modes,
                           const nk_free_path_rays *rays, nk_free_path_columns_report *report);
 
+/* Free-path maps: the rays of nk_free_paths binned on the device by the cell of their START point -- where in the structure
+ * the walls cut the heat flow (the Fuchs-Sondheimer local conductivity).  The flight, the per-mode sums and the per-ray
+ * outputs are those of nk_free_paths with the same arguments, bit for bit.  The grid is the field's (nk_field): cell of a
+ * start point = floor((x - lo) * (1 / h)) per axis, an index outside [0, n) or a NaN clamped into the edge cell and counted in
+ * `clamped`; cell order (ix * ny + iy) * nz + iz.  Per cell one line of NK_FREE_MAP_LINE 64-bit integers:
+ *   0          N, the rays that started in the cell
+ *   1 + 3a + b the sum of w_a D_b 2^k_K, w = `weight` of the ray's LIST ENTRY (on the host C_m v_m / (Q V); also after
+ *              reflections into other modes), D the ray's displacement
+ *   10, 11, 12 the sums of the rays' final weights 2^k_P that ended at a reservoir (p_res), at a diffuse wall (p_wall), or were
+ *              cut off by w_min or max_segments (w_left); a miss, a reflection into a mode that does not live and a ray
+ *              without a cast add nothing: p_int of a cell = N - p_res - p_wall - w_left
+ *   13         the sum of the flight times 2^k_T
+ *   14, 15     zero
+ * Every term is rounded to nearest even after the scaling and added as an integer in two's complement (an exact zero is not
+ * added), so the cells are the same bits in any order of the rays and sums of calls with equal scales are the cells of the
+ * joint call.  Scales: k = the largest with cap B 2^k <= 2^62, cap = max(rays of the call, `capacity`), B_K = max(largest
+ * |weight| component, `weight_bound`) x the largest |v_m| component x tau_m over ALL modes with tau > 0, B_P = 1, B_T = the
+ * largest positive tau.  A term above its bound is left out and counted in `overflow`, and the call returns NK_ERR_CAPACITY with a
+ * text that names the sum: a sum never wraps silently.  For a mode set with inversion symmetry sum_m C_m v_a E[D_b | x0 = x] is
+ * the local conductivity tensor at x in the relaxation-time picture: exact on the terms that make the global estimate exact,
+ * an approximation otherwise (reservoirs that end flights along the transport direction): an estimate, not a replacement for
+ * the run's field.  Buffers of the call alone; neither the particle store, the step counter, the field, the mode tally nor
+ * the state of nk_free_paths (nk_free_paths_info) is touched. */
+#define NK_FREE_MAP_LINE 16
+typedef struct {
+    int32_t n[3]; int32_t pad_;
+    double lo[3], h[3];          /* the field's grid convention */
+    const double *weight;        /* [n_list * 3] per list entry (n_list = Q*J when args->modes is NULL) */
+    int64_t capacity;            /* floor under the ray count when the scales are derived; 0: none */
+    double weight_bound;         /* floor under max |weight|; 0: none */
+    int32_t *ray_cell;           /* [rays] the start cell of every ray, or NULL */
+    double *ray_w;               /* [rays] the weight that went to word 10, 11 or 12, zero otherwise, or NULL */
+} nk_free_path_grid;
+typedef struct {
+    int64_t rays, casts, missed, capped, clamped, overflow;
+    int32_t k_K, k_P, k_T, geometry_mode, calls, pad_;
+    double B_K, B_T;
+    int64_t bytes;               /* device memory the last call allocated (and freed) */
+    double seconds;              /* device time of the kernel, from HIP events */
+} nk_free_path_map_report;
+/* NK_ERR_ARG, with a text that names the cause: every refusal of nk_free_paths, in its words; `weight` NULL or not finite; n or h
+ * not positive; more than 2^24 cells; `cells` NULL.  Nothing is launched or allocated then and the report is all zero. */
+int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *args, const nk_free_path_grid *grid, int64_t *cells /* [ncells*16] */,
+                      const nk_free_path_modes *modes, const nk_free_path_rays *rays, nk_free_path_map_report *report);
+/* The report of the last map call; all zero on a context that never made one. */
+int nk_free_paths_map_info(nk_ctx *ctx, nk_free_path_map_report *out);
+
 /* Replica groups: R contexts that hold the same problem under different seeds (the runs behind an error bar) are stepped by
  * shared launches -- per step ONE sweep and ONE tail launch for all of them instead of R of each, and one wait per call.  A
  * workgroup of the shared launch finds its member and runs that member's step exactly as nk_step would: the rows and the

@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path` and `--free_path_sweep`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep` and `--free_path_map`."""
 import argparse
 import os
 import sys
@@ -81,6 +81,12 @@ def initialise_parser(debug_flag=False):
            'k_free_path_sweep.txt (one line per value: kappa along the axis, its standard error, the bulk value, their ratio) and '
            'free_path_sweep.npz (per value the tensors, the per-mode suppression, the accumulation over the mean free path on '
            'one grid); off by default')
+    a('--free_path_map', default=[], type=str, nargs='*',
+      help='nx ny nz [count|solid]: with --free_path N, also bin the same rays on the GPU by the cell of their start point on a '
+           'grid of nx x ny x nz cells over the bounding box (the grid of --field_grid) and write free_path_map.npz and '
+           'free_path_map.vtk: the local conductivity tensor per cell, its ratio to the bulk value along the axis, the rays per '
+           'cell and how they ended -- where the walls cut the heat flow, before a step is run (an estimate); count divides by '
+           'the rays a cell received (the default), solid by the exact volume of solid in it; off by default')
     a('--replicas', default=[1], type=int, nargs=1,
       help='R: run the same problem under the seeds seed, seed + 1, ..., seed + R - 1 (an error bar on the conductivity); '
            'every replica writes its files to replica_<k> of the results folder, ensemble.txt holds the mean, the standard '

@@ -24,6 +24,7 @@
 #include "nk_group.h"
 #include "nk_freepath.h"
 #include "nk_freecols.h"
+#include "nk_freemap.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -148,6 +149,7 @@ struct nk_ctx {
     // free-path sampling (nk_free_paths, k_free_paths; nk_freepath.hip): the last call's report -- nothing is kept on the device
     nk_free_path_report fp_last = {};
     int32_t fc_calls = 0;        // nk_free_paths_columns calls so far (k_free_columns; nk_freecols.hip)
+    nk_free_path_map_report fm_last = {};   // the last nk_free_paths_map call's report (k_free_map; nk_freemap.hip)
 };
 
 #define NK_HIP(call)                                                                                   \
@@ -4100,5 +4102,163 @@ int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *a, int32_t n_col
     }
     ctx->fc_calls = r.calls;
     if (rep) *rep = r;
+    return NK_OK;
+}
+
+// k_free_map (nk_freemap.hip): the rays of nk_free_paths binned by their start cell.  Buffers of this call alone, as above; the
+// field, the mode tally and nk_free_paths' own report (fp_last) are not touched.
+int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_path_grid *gr, int64_t *cells, const nk_free_path_modes *pm,
+                      const nk_free_path_rays *pr, nk_free_path_map_report *rep) {
+    if (rep) memset(rep, 0, sizeof(*rep));
+    NK_ARG(ctx && a && gr, "nk_free_paths_map: NULL argument");
+    NK_ARG(ctx->have_material, "nk_free_paths_map: no material (nk_set_material first)");
+    NK_ARG(ctx->have_mesh, "nk_free_paths_map: no mesh (nk_set_mesh first)");
+    NkDev &d = ctx->d;
+    NK_ARG(a->tau, "nk_free_paths_map: tau is NULL (the lifetimes of all Q*J modes at the temperature of the estimate)");
+    NK_ARG(a->n_samples > 0, "nk_free_paths_map: n_samples = " + std::to_string(a->n_samples) + " must be positive");
+    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, "nk_free_paths_map: max_segments and w_min must not be negative");
+    const int64_t nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
+    NK_ARG(nlist >= 0, "nk_free_paths_map: n_modes must not be negative");
+    if (a->modes)
+        for (int64_t i = 0; i < nlist; ++i)
+            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, "nk_free_paths_map: mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
+                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
+    for (int fc = 0; fc < d.Fc; ++fc)
+        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
+               "nk_free_paths_map: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
+    NK_ARG(a->x0 || d.nS > 0, "nk_free_paths_map: no start points (x0) and the mesh was set without its volume tables (simplices)");
+    const int64_t rays = nlist * (int64_t)a->n_samples;
+    NK_ARG(rays < (1ll << 31), "nk_free_paths_map: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    // the map's own arguments
+    NK_ARG(gr->weight, "nk_free_paths_map: weight is NULL (a weight vector per list entry, C_m v_m / (Q V))");
+    double wmax = 0.0;
+    for (int64_t i = 0; i < nlist * 3; ++i) {
+        NK_ARG(std::isfinite(gr->weight[i]), "nk_free_paths_map: weight of list entry " + std::to_string((long long)(i / 3)) + " is not finite");
+        wmax = std::max(wmax, fabs(gr->weight[i]));
+    }
+    NK_ARG(gr->n[0] > 0 && gr->n[1] > 0 && gr->n[2] > 0, "nk_free_paths_map: the cell counts n must be positive");
+    for (int c = 0; c < 3; ++c)
+        NK_ARG(gr->h[c] > 0.0 && std::isfinite(gr->h[c]) && std::isfinite(gr->lo[c]), "nk_free_paths_map: the cell sizes h must be positive (and lo finite)");
+    const int64_t ncells = (int64_t)gr->n[0] * gr->n[1] * gr->n[2];
+    NK_ARG(ncells <= (1ll << 24), "nk_free_paths_map: " + std::to_string((long long)ncells) + " cells are more than the grid takes (2^24)");
+    NK_ARG(cells, "nk_free_paths_map: cells is NULL (the result, [ncells * 16] 64-bit integers)");
+    NK_ARG(gr->capacity >= 0 && gr->weight_bound >= 0.0 && std::isfinite(gr->weight_bound), "nk_free_paths_map: capacity and weight_bound must not be negative");
+    NK_ARG(ctx->h_vg.size() == (size_t)d.M * 3, "nk_free_paths_map: no group velocities (nk_set_material first)");
+    // bounds and scales (DESIGN.md "Free-path maps"): over a ray sum W g <= 1, so |D_b| <= Lambda_max and T <= tau_max
+    double lam = 0.0, tmax = 0.0;
+    for (int64_t m = 0; m < d.M; ++m) {
+        const double t = a->tau[m];
+        if (!(t > 0.0)) continue;
+        NK_ARG(std::isfinite(t), "nk_free_paths_map: tau of mode " + std::to_string((long long)m) + " is not finite");
+        const double *v = &ctx->h_vg[3 * (size_t)m];
+        const double vi = std::max(std::max(fabs(v[0]), fabs(v[1])), fabs(v[2]));
+        lam = std::max(lam, vi * t);
+        tmax = std::max(tmax, t);
+    }
+    nk_free_path_map_report r;
+    memset(&r, 0, sizeof(r));
+    r.rays = rays;
+    r.B_K = std::max(wmax, gr->weight_bound) * lam;
+    r.B_T = tmax;
+    const int64_t cap = std::max<int64_t>(rays, gr->capacity);
+    r.k_K = nk_field_k(r.B_K, cap); r.k_P = nk_field_k(1.0, cap); r.k_T = nk_field_k(r.B_T, cap);
+    NK_HIP(hipSetDevice(ctx->device));
+    const bool want_rays = pr && (pr->D || pr->T || pr->segments || pr->end || pr->x0);
+    NK_BUF(int32_t, dmodes, a->modes, a->modes ? nlist : 0);
+    NK_BUF(double, dtau, a->tau, d.M);
+    NK_BUF(double, dx0, a->x0, a->x0 ? rays * 3 : 0);
+    NK_BUF(double, dwt, gr->weight, nlist * 3);
+    NK_BUF(double, drows, nullptr, nlist * NK_FP_ROW);
+    NK_BUF(unsigned long long, dcnt, nullptr, nlist * NK_FP_CNT);
+    NK_BUF(unsigned long long, dgrid, nullptr, (ncells + 1) * NK_FREE_MAP_LINE);
+    NK_BUF(double, drD, nullptr, (want_rays && pr->D) ? rays * 3 : 0);
+    NK_BUF(double, drT, nullptr, (want_rays && pr->T) ? rays : 0);
+    NK_BUF(double, drx, nullptr, (want_rays && pr->x0) ? rays * 3 : 0);
+    NK_BUF(int32_t, drs, nullptr, (want_rays && pr->segments) ? rays : 0);
+    NK_BUF(int32_t, dre, nullptr, (want_rays && pr->end) ? rays : 0);
+    NK_BUF(int32_t, drc, nullptr, gr->ray_cell ? rays : 0);
+    NK_BUF(double, drw, nullptr, gr->ray_w ? rays : 0);
+    NkFreeDev f;
+    f.modes = a->modes ? dmodes.p : nullptr;
+    f.nlist = (int32_t)nlist; f.n = a->n_samples;
+    f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
+    f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
+    f.tau = dtau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? dx0.p : nullptr;
+    f.seed = a->seed ? a->seed : d.seed;
+    f.rows = drows.p; f.counts = dcnt.p;
+    f.ray_D = (want_rays && pr->D) ? drD.p : nullptr; f.ray_T = (want_rays && pr->T) ? drT.p : nullptr;
+    f.ray_x0 = (want_rays && pr->x0) ? drx.p : nullptr;
+    f.ray_seg = (want_rays && pr->segments) ? drs.p : nullptr; f.ray_end = (want_rays && pr->end) ? dre.p : nullptr;
+    NkFreeMapDev g;
+    for (int c = 0; c < 3; ++c) { g.lo[c] = gr->lo[c]; g.inv_h[c] = 1.0 / gr->h[c]; g.n[c] = gr->n[c]; }
+    g.ncells = (int32_t)ncells;
+    g.weight = dwt.p;
+    g.sK = ldexp(1.0, r.k_K); g.sP = ldexp(1.0, r.k_P); g.sT = ldexp(1.0, r.k_T);
+    g.BK = r.B_K; g.BP = 1.0; g.BT = r.B_T;
+    g.grid = dgrid.p;
+    g.ray_cell = gr->ray_cell ? drc.p : nullptr; g.ray_w = gr->ray_w ? drw.p : nullptr;
+    r.geometry_mode = nk_geom_mode(ctx);
+    r.calls = ctx->fm_last.calls + 1;
+    r.bytes = (a->modes ? nlist * 4 : 0) + (int64_t)d.M * 8 + (a->x0 ? rays * 24 : 0) + nlist * 24 + nlist * (NK_FP_ROW + NK_FP_CNT) * 8 +
+              (ncells + 1) * NK_FREE_MAP_LINE * 8 + (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) + (f.ray_x0 ? rays * 24 : 0) +
+              (f.ray_seg ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0) + (g.ray_cell ? rays * 4 : 0) + (g.ray_w ? rays * 8 : 0);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipMemsetAsync(dgrid.p, 0, (size_t)(ncells + 1) * NK_FREE_MAP_LINE * 8, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
+    if (e == hipSuccess) e = nk_free_map_launch(d, f, g, r.geometry_mode, nk_lds(ctx, true), ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    NK_HIP(e);
+    r.seconds = 1e-3 * (double)ms;
+    std::vector<double> rows((size_t)nlist * NK_FP_ROW);
+    std::vector<unsigned long long> cnt((size_t)nlist * NK_FP_CNT);
+    NK_HIP(drows.get(rows.data(), nlist * NK_FP_ROW));
+    NK_HIP(dcnt.get(cnt.data(), nlist * NK_FP_CNT));
+    for (int64_t i = 0; i < nlist; ++i) {
+        const double *w = &rows[(size_t)i * NK_FP_ROW];
+        if (pm) {
+            for (int c = 0; c < 3; ++c) { if (pm->D) pm->D[3 * i + c] = w[c]; if (pm->D2) pm->D2[3 * i + c] = w[3 + c]; }
+            if (pm->T) pm->T[i] = w[6];
+            if (pm->hits) pm->hits[i] = w[7];
+            if (pm->p_res) pm->p_res[i] = w[8];
+            if (pm->p_wall) pm->p_wall[i] = w[9];
+            if (pm->w_left) pm->w_left[i] = w[10];
+            if (pm->p_int) pm->p_int[i] = w[11];
+        }
+        r.casts += (int64_t)cnt[(size_t)i * NK_FP_CNT]; r.missed += (int64_t)cnt[(size_t)i * NK_FP_CNT + 1]; r.capped += (int64_t)cnt[(size_t)i * NK_FP_CNT + 2];
+    }
+    if (want_rays) {
+        if (pr->D) NK_HIP(drD.get(pr->D, rays * 3));
+        if (pr->T) NK_HIP(drT.get(pr->T, rays));
+        if (pr->x0) NK_HIP(drx.get(pr->x0, rays * 3));
+        if (pr->segments) NK_HIP(drs.get(pr->segments, rays));
+        if (pr->end) NK_HIP(dre.get(pr->end, rays));
+    }
+    if (gr->ray_cell) NK_HIP(drc.get(gr->ray_cell, rays));
+    if (gr->ray_w) NK_HIP(drw.get(gr->ray_w, rays));
+    NK_HIP(hipMemcpy(cells, dgrid.p, (size_t)ncells * NK_FREE_MAP_LINE * 8, hipMemcpyDeviceToHost));
+    unsigned long long hdr[NK_FREE_MAP_LINE];
+    NK_HIP(hipMemcpy(hdr, dgrid.p + (size_t)ncells * NK_FREE_MAP_LINE, sizeof(hdr), hipMemcpyDeviceToHost));
+    r.clamped = (int64_t)hdr[NK_FM_CLAMPED];
+    r.overflow = (int64_t)(hdr[NK_FM_OVK] + hdr[NK_FM_OVP] + hdr[NK_FM_OVT]);
+    ctx->fm_last = r;
+    if (rep) *rep = r;
+    if (r.overflow) {
+        ctx->err = "nk_free_paths_map: map overflow: " + std::to_string((long long)hdr[NK_FM_OVK]) + " term(s) of w D above B_K = " + std::to_string(r.B_K) +
+                   ", " + std::to_string((long long)hdr[NK_FM_OVP]) + " weight(s) above B_P = 1, " + std::to_string((long long)hdr[NK_FM_OVT]) +
+                   " flight time(s) above B_T = " + std::to_string(r.B_T) + "; they were left out of the sums";
+        return NK_ERR_CAPACITY;
+    }
+    return NK_OK;
+}
+int nk_free_paths_map_info(nk_ctx *ctx, nk_free_path_map_report *out) {
+    NK_ARG(ctx && out, "nk_free_paths_map_info: NULL argument");
+    *out = ctx->fm_last;
     return NK_OK;
 }

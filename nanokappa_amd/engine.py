@@ -92,7 +92,8 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_field_groups', 'nk_get_field_groups', 'nk_tally_field_groups_state', 'nk_field_groups_info',
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
-           'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info', 'nk_free_paths_columns']
+           'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info', 'nk_free_paths_columns',
+           'nk_free_paths_map', 'nk_free_paths_map_info']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -150,6 +151,21 @@ class nk_free_path_columns_report(C.Structure):
                 ('missed', C.c_int64 * FREE_PATH_MAX_COLUMNS), ('capped', C.c_int64 * FREE_PATH_MAX_COLUMNS),
                 ('n_columns', C.c_int32), ('tile', C.c_int32), ('launches', C.c_int32), ('geometry_mode', C.c_int32),
                 ('calls', C.c_int32), ('pad_', C.c_int32), ('bytes', C.c_int64), ('seconds', C.c_double)]
+
+
+FREE_MAP_LINE = 16           # NK_FREE_MAP_LINE
+
+
+class nk_free_path_grid(C.Structure):
+    _fields_ = [('n', C.c_int32 * 3), ('pad_', C.c_int32), ('lo', C.c_double * 3), ('h', C.c_double * 3), ('weight', c_dp),
+                ('capacity', C.c_int64), ('weight_bound', C.c_double), ('ray_cell', c_ip), ('ray_w', c_dp)]
+
+
+class nk_free_path_map_report(C.Structure):
+    _fields_ = [('rays', C.c_int64), ('casts', C.c_int64), ('missed', C.c_int64), ('capped', C.c_int64), ('clamped', C.c_int64),
+                ('overflow', C.c_int64), ('k_K', C.c_int32), ('k_P', C.c_int32), ('k_T', C.c_int32), ('geometry_mode', C.c_int32),
+                ('calls', C.c_int32), ('pad_', C.c_int32), ('B_K', C.c_double), ('B_T', C.c_double), ('bytes', C.c_int64),
+                ('seconds', C.c_double)]
 
 
 class nk_group_report(C.Structure):
@@ -252,6 +268,9 @@ def load_library():
     L.nk_free_paths.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.POINTER(nk_free_path_modes), C.POINTER(nk_free_path_rays),
                                 C.POINTER(nk_free_path_report)]
     L.nk_free_paths_info.argtypes = [C.c_void_p, C.POINTER(nk_free_path_report)]
+    L.nk_free_paths_map.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.POINTER(nk_free_path_grid), C.POINTER(C.c_int64),
+                                    C.POINTER(nk_free_path_modes), C.POINTER(nk_free_path_rays), C.POINTER(nk_free_path_map_report)]
+    L.nk_free_paths_map_info.argtypes = [C.c_void_p, C.POINTER(nk_free_path_map_report)]
     L.nk_free_paths_columns.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.c_int32, C.POINTER(nk_free_path_modes),
                                         C.POINTER(nk_free_path_rays), C.POINTER(nk_free_path_columns_report)]
     _lib = L
@@ -821,6 +840,80 @@ class Engine(object):
                                launches=int(rep.launches), geometry_mode=int(rep.geometry_mode), calls=int(rep.calls),
                                bytes=int(rep.bytes), seconds=float(rep.seconds)))
         return out
+
+    @staticmethod
+    def _free_path_map_report(r):
+        return dict(rays=int(r.rays), casts=int(r.casts), missed=int(r.missed), capped=int(r.capped), clamped=int(r.clamped),
+                    overflow=int(r.overflow), k_K=int(r.k_K), k_P=int(r.k_P), k_T=int(r.k_T), geometry_mode=int(r.geometry_mode),
+                    calls=int(r.calls), B_K=float(r.B_K), B_T=float(r.B_T), bytes=int(r.bytes), seconds=float(r.seconds))
+
+    def free_path_map(self, tau, weight, lo, h, n_cells, n=64, modes=None, max_segments=0, w_min=0.0, x0=None, seed=0, rays=True,
+                      capacity=0, weight_bound=0.0):
+        """Free-path map (nk_free_paths_map; k_free_map): the rays of free_paths(tau, n, modes, ...) binned on the device by the
+        cell of their START point on the grid (lo, h, n_cells) -- the field's convention.  weight [L, 3]: per list entry the
+        vector w whose products w_a D_b are summed (free_map.weights: C_m v_m / (Q V)); capacity / weight_bound: floors under the
+        ray count and under max |weight| when the scales are derived (pin them to add the cells of several calls).  Returns the
+        dict of free_paths -- the same bits -- plus cells [nx, ny, nz, 16] int64 (free_map.tally states the layout) and the map's
+        report (rays, casts, missed, capped, clamped, overflow, k_K, k_P, k_T, B_K, B_T, geometry_mode, calls, bytes, seconds);
+        with rays=True also the per-ray outputs of free_paths and ray_cell [L, n] (flat cell index), ray_w [L, n] (the final weight
+        that went to p_res, p_wall or w_left; 0 otherwise).  Touches neither the particles, the step counter, the field nor
+        free_paths_info()."""
+        a = nk_free_path_args()
+        t = None if tau is None else _d(np.ravel(tau))
+        if t is not None and self.M > 0 and t.shape[0] != self.M:
+            raise NkError('free_path_map: tau has %d entries, the material %d modes' % (t.shape[0], self.M))
+        if modes is None and t is not None and self.M > 0:
+            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & (t > 0))[0]
+        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
+        L = self.M if ml is None else int(ml.shape[0])
+        n = int(n)
+        xs = None
+        if x0 is not None:
+            xs = _d(x0)
+            if xs.size != L * max(n, 0) * 3:
+                raise NkError('free_path_map: x0 needs %d x %d x 3 entries, got %d' % (L, n, xs.size))
+        w = None
+        if weight is not None:
+            w = _d(weight)
+            if w.size != L * 3:
+                raise NkError('free_path_map: weight needs %d x 3 entries (a vector per list entry), got %d' % (L, w.size))
+        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
+        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
+        nc = [int(k) for k in np.ravel(n_cells)]
+        g = nk_free_path_grid()
+        g.n[:] = nc
+        g.lo[:] = [float(x) for x in np.ravel(lo)]
+        g.h[:] = [float(x) for x in np.ravel(h)]
+        g.weight, g.capacity, g.weight_bound = _p(w), int(capacity), float(weight_bound)
+        ok = min(nc) > 0 and nc[0] * nc[1] * nc[2] <= (1 << 24)         # (a refused call writes nothing)
+        cells = np.zeros(tuple(nc) + (FREE_MAP_LINE,) if ok else (1,), dtype=np.int64)
+        nn = max(n, 0)
+        out = dict(D=np.zeros((L, 3)), D2=np.zeros((L, 3)), T=np.zeros(L), hits=np.zeros(L), p_res=np.zeros(L), p_wall=np.zeros(L),
+                   w_left=np.zeros(L), p_int=np.zeros(L))
+        pm = nk_free_path_modes()
+        for k in out:
+            setattr(pm, k, _p(out[k]))
+        pr = nk_free_path_rays()
+        if rays:
+            ro = dict(ray_D=np.zeros((L, nn, 3)), ray_T=np.zeros((L, nn)), ray_segments=np.zeros((L, nn), dtype=np.int32),
+                      ray_end=np.zeros((L, nn), dtype=np.int32), ray_x0=np.zeros((L, nn, 3)), ray_cell=np.zeros((L, nn), dtype=np.int32),
+                      ray_w=np.zeros((L, nn)))
+            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
+            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
+            g.ray_cell, g.ray_w = _p(ro['ray_cell'], c_ip), _p(ro['ray_w'])
+            out.update(ro)
+        rep = nk_free_path_map_report()
+        self._ck(self.L.nk_free_paths_map(self.h, C.byref(a), C.byref(g), cells.ctypes.data_as(C.POINTER(C.c_int64)) if ok else None,
+                                          C.byref(pm), C.byref(pr) if rays else None, C.byref(rep)), 'nk_free_paths_map')
+        out.update(modes=(np.arange(self.M, dtype=np.int32) if ml is None else ml.copy()), n=n, cells=cells,
+                   report=self._free_path_map_report(rep))
+        return out
+
+    def free_path_map_info(self):
+        """The report of the last free_path_map call on this engine; all zero (calls = 0, bytes = 0) when there was none."""
+        rep = nk_free_path_map_report()
+        self._ck(self.L.nk_free_paths_map_info(self.h, C.byref(rep)), 'nk_free_paths_map_info')
+        return self._free_path_map_report(rep)
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

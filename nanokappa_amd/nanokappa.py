@@ -8,6 +8,8 @@ import re
 import sys
 from datetime import datetime, timedelta
 
+import numpy as np
+
 from .argument_parser import read_args, generate_results_folder
 from .geometry import Geometry
 from .phonon import Phonon
@@ -41,6 +43,8 @@ def main(argv=None):
     fp_n, fp_T, fp_segments = free_path_option(getattr(args, 'free_path', None))     # (refused here, before anything is set up)
     from .free_sweep import sweep_option
     sw_kind, sw_values = sweep_option(getattr(args, 'free_path_sweep', None), fp_n)
+    from .free_map import free_path_map_option
+    fm_n, fm_kind = free_path_map_option(getattr(args, 'free_path_map', None), fp_n)
     args = generate_results_folder(args)
     out = None
     # nanokappa.py:34-36 compares the parsed value with 'file'; an explicit `--output file` arrives as the list ['file'] and
@@ -88,6 +92,14 @@ def main(argv=None):
                 for c in sw['columns']:
                     print('    %s %g: kappa_%s%s = %.4f +- %.4f W/m K, bulk %.4f W/m K' %
                           (sw_kind, c['value'], 'xyz'[a], 'xyz'[a], c['kappa'][a, a], c['kappa_se'][a, a], c['kappa_bulk'][a, a]))
+        if fm_n is not None:                   # --free_path_map: the same rays, binned by their start cell
+            fm = pop.free_path_map(fm_n, n=fp_n, T=fp_T, max_segments=fp_segments, normalise=fm_kind)
+            if fm is not None:
+                a = fm['axis']
+                sup = fm['suppression'][np.isfinite(fm['suppression'])]
+                print('  map on %d x %d x %d cells (%s): kappa_%s%s / bulk from %.4f to %.4f over the cells; %d start points clamped' %
+                      (fm['n'] + (fm_kind, 'xyz'[a], 'xyz'[a], sup.min() if sup.size else np.nan, sup.max() if sup.size else np.nan,
+                                  fm['report']['clamped'])))
     flag = True
     while flag:
         # batches end on the 100-step bookkeeping boundary, so stop criteria are checked as often as the

@@ -26,6 +26,7 @@ from . import field_groups as FG
 from . import modes as MD
 from . import free_path as FP
 from . import free_sweep as FS
+from . import free_map as FM
 from .engine import Engine
 from .sharding import shard_range
 
@@ -593,6 +594,54 @@ class Population(Constants):
             FS.write_k_free_path_sweep(FS.k_free_path_sweep_path(self.results_folder_name), sw)
             FS.write_free_path_sweep_npz(FS.free_path_sweep_npz_path(self.results_folder_name), sw)
         return sw
+
+    def free_path_map(self, n_cells, n=FP.N_DEFAULT, T=None, modes=None, normalise='count', axis=None, x0=None, seed=0, write=True,
+                      max_segments=FP.MAX_SEGMENTS_DEFAULT, w_min=FP.W_MIN_DEFAULT):
+        """Where in the structure the walls cut the heat flow: the rays of free_paths binned on the GPU by the cell of their
+        start point (Engine.free_path_map) on the grid field.grid_from_bounds(geometry.bounds, n_cells), and normalised per cell
+        (free_map.normalise): kappa [nx, ny, nz, 3, 3], the suppression against the bulk value along `axis`, N, the shares of
+        the rays' weight by their end, the mean flight time.  normalise 'count' divides by the observed rays per mode of a
+        cell, 'solid' by the expected ones from the exact solid volume of every cell (engine.cell_solid_volume, called once),
+        which is unbiased and sums back to the global tensor.  The other arguments as free_paths.  Returns the map's dict with
+        lo, h, n, cells, report, kappa_bulk, kappa_global and `summary`, free_path.summarise()'s result for the same rays; with a
+        results folder writes free_path_map.npz and free_path_map.vtk.  An estimate (see free_map.py), not a replacement for the
+        run's field.  Particles, step counter and field are not touched.  With several ranks rank 0 computes and writes; the
+        others return None."""
+        if self.rank != 0:
+            return None
+        if normalise not in FM.KINDS:
+            raise ValueError('free_path_map: normalise must be count or solid')
+        ph, geo = self._ph, self._geo
+        T = self._mean_reservoir_T() if T is None else float(T)
+        tau = FP.lifetimes(ph, T)
+        if modes is None:
+            modes = FP.default_modes(ph.group_vel, tau)
+        modes = np.asarray(modes, dtype=np.int32).ravel()
+        if axis is None:
+            axis = int(getattr(self, 'slice_axis', 0) or 0)
+        lo, h, nc = FD.grid_from_bounds(geo.bounds, n_cells)
+        qv = ph.number_of_qpoints * ph.volume_unitcell
+        vg = np.asarray(ph.group_vel, dtype=np.float64).reshape(-1, 3)
+        C = FP.mode_heat_capacity(np.asarray(ph.omega, dtype=np.float64).ravel()[modes], T, self.hbar, self.kb)
+        res = self.engine.free_path_map(tau, FM.weights(C, vg[modes], qv), lo, h, nc, n=int(n), modes=modes, max_segments=int(max_segments),
+                                        w_min=float(w_min), x0=x0, seed=int(seed), rays=False)
+        s = FP.summarise(res, ph.omega, ph.group_vel, tau, qv, T, axis=axis, hbar=self.hbar, kb=self.kb)
+        fraction = None
+        if normalise == 'solid':
+            from .engine import cell_solid_volume
+            V = cell_solid_volume(geo.mesh.vertices, geo.mesh.faces, lo, h, nc, device=int(getattr(self.args, 'device', [0])[0]))
+            fraction = V / float(np.prod(h))
+        m = FM.normalise(res['cells'], res['report'], int(n), modes.shape[0], kind=normalise, solid_fraction=fraction,
+                         cell_volume=float(np.prod(h)), kappa_bulk=s['kappa_bulk'], axis=axis)
+        m.update(lo=lo, h=h, n=nc, cells=res['cells'], report=res['report'], solid_fraction=fraction, kappa_bulk=s['kappa_bulk'],
+                 kappa_global=s['kappa'], T=T, n_samples=int(n), n_list=int(modes.shape[0]), summary=s)
+        self.free_path_map_last = m
+        if write and self.results_folder_name:
+            FM.write_free_path_map_npz(FM.free_path_map_npz_path(self.results_folder_name), m)
+            FM.write_free_path_map_vtk(FM.free_path_map_vtk_path(self.results_folder_name), m,
+                                       title='nanokappa free-path map: kappa_%s%s at T = %g K, %d rays per mode, %s' %
+                                             ('xyz'[axis], 'xyz'[axis], T, int(n), normalise))
+        return m
 
     def free_path_report(self):
         """The engine's report of its last free-path call; calls = 0 and bytes = 0 when there was none."""

@@ -1,0 +1,396 @@
+"""Free-path maps on the GPU (Engine.free_path_map; k_free_map): the rows and rays are nk_free_paths' own bit for bit; the cells
+are free_map.tally of the call's own per-ray outputs bit for bit; clamping; order and list independence; the sum identity; the
+closed form per slab cell; non-interference; the refusals; Population.free_path_map and --free_path_map.
+
+The smallest shapes that still reach every branch: n = 100 (a partly empty second pass of lanes), the cap, reflections into other
+modes, the face tree, cells outside the solid.  report['overflow'] == 0 is asserted on every call (map_call())."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import free_path_cases as FC
+from nanokappa_amd import field as FD
+from nanokappa_amd import free_map as FM
+from nanokappa_amd import free_path as FP
+from test_gpu_free_path import fp_engine, wave_sum
+from test_free_map_host import case_weights, profile_with_errors, closed_form_profile
+
+pytestmark = pytest.mark.gpu
+
+MODE_KEYS = ('D', 'D2', 'T', 'hits', 'p_res', 'p_wall', 'w_left', 'p_int')
+RAY_KEYS = ('ray_D', 'ray_T', 'ray_segments', 'ray_end', 'ray_x0')
+GRIDS = {'ttp': (4, 3, 2), 'ttrrp_k': (4, 3, 2), 'corrugated': (5, 4, 3), 'wire72': (5, 4, 3)}
+
+
+def bounds(ct):
+    return np.asarray(ct['mesh']['bounds'], dtype=np.float64).reshape(2, 3)
+
+
+def parity_inputs(name):
+    """Case, mode list, n, max_segments, seed of FC.PARITY[name], start points from NumPy's generator, and the weights."""
+    p = FC.PARITY[name]
+    ct = FC.case(p['case'])
+    modes = np.asarray(p['modes'](ct), dtype=np.int32)
+    x0 = FC.uniform_points(ct, modes.shape[0], p['n'], p['seed'])
+    return ct, modes, p['n'], p['max_segments'], p['seed'], x0, case_weights(ct, modes)[1]
+
+
+def map_call(eng, ct, modes, w, grid, **kw):
+    """Engine.free_path_map on grid = (lo, h, n); overflow == 0 on every call."""
+    lo, h, n = grid
+    got = eng.free_path_map(FC.lifetimes(ct), w, lo, h, n, modes=modes, **kw)
+    assert got['report']['overflow'] == 0 and got['cells'].shape == tuple(n) + (16,) and got['cells'].dtype == np.int64
+    return got
+
+
+def host_tally(got, w, grid):
+    lo, h, n = grid
+    r = got['report']
+    ns = got['ray_T'].shape[1]
+    return FM.tally(got['ray_x0'], got['ray_D'], got['ray_T'], got['ray_w'], got['ray_end'], np.repeat(w, ns, axis=0), lo, h, n,
+                    r['k_K'], r['k_P'], r['k_T'])
+
+
+def assert_cells_are_the_rule(got, w, grid, ct, tau):
+    lo, h, n = grid
+    assert np.array_equal(got['cells'], host_tally(got, w, grid)), 'cells differ from free_map.tally of the call\'s own rays'
+    c, out = FD.cell_index(got['ray_x0'].reshape(-1, 3), lo, h, n)
+    assert np.array_equal(got['ray_cell'].ravel(), (c[:, 0] * n[1] + c[:, 1]) * n[2] + c[:, 2])
+    assert got['report']['clamped'] == int(out.sum())
+    assert got['cells'][..., 0].sum() == got['report']['rays'] == got['ray_T'].size
+    assert not got['cells'][..., 14:].any()
+    end, rw = got['ray_end'], got['ray_w']
+    assert wave_sum(np.where(end == 1, rw, 0.0)).tobytes() == got['p_res'].tobytes()
+    assert wave_sum(np.where(end == 2, rw, 0.0)).tobytes() == got['p_wall'].tobytes()
+    assert wave_sum(np.where((end == 0) | (end == 4), rw, 0.0)).tobytes() == got['w_left'].tobytes()
+    assert np.all(rw[end == 3] == 0.0) and np.all(rw[(end == 1) | (end == 2) | (end == 4)] > 0.0)
+    s = FM.scales(w, FC.group_vel(ct), tau, got['report']['rays'])
+    for k in ('k_K', 'k_P', 'k_T', 'B_K', 'B_T'):
+        assert got['report'][k] == s[k], k
+
+
+@pytest.mark.parametrize('name', ['ttp', 'ttrrp_k', 'wire72'])
+def test_rows_and_rays_are_free_paths_own(name):
+    """Every per-mode array and every per-ray array of free_path_map equals free_paths with the same arguments, tobytes() equal;
+    rays, casts, missed and capped are equal."""
+    ct, modes, n, ms, seed, x0, w = parity_inputs(name)
+    eng = fp_engine(ct, seed=99)
+    tau = FC.lifetimes(ct)
+    ref = eng.free_paths(tau, n=n, modes=modes, max_segments=ms, x0=x0, seed=seed, rays=True)
+    before = eng.free_paths_info()
+    grid = FD.grid_from_bounds(bounds(ct), GRIDS[name])
+    got = map_call(eng, ct, modes, w, grid, n=n, max_segments=ms, x0=x0, seed=seed, rays=True)
+    assert eng.free_paths_info() == before
+    eng.close()
+    for k in MODE_KEYS + RAY_KEYS:
+        assert got[k].tobytes() == ref[k].tobytes(), k
+    for k in ('rays', 'casts', 'missed', 'capped', 'geometry_mode'):
+        assert got['report'][k] == ref['report'][k], k
+    assert got['report']['geometry_mode'] == (2 if name == 'wire72' else 1)
+    if name == 'ttp':
+        assert got['report']['capped'] > 1000 and (got['ray_end'] == 4).any() and n == 100
+    if name == 'ttrrp_k':
+        assert (got['ray_end'] == 2).any() and (got['ray_end'] == 1).any()
+
+
+@pytest.mark.parametrize('name', ['ttp', 'ttrrp_k', 'corrugated', 'wire72'])
+def test_cells_are_the_rule_bit_for_bit(name):
+    """cells == free_map.tally of the call's own ray_x0, ray_D, ray_T, ray_w, ray_end and weights at the report's scales;
+    ray_cell is field.cell_index's clamped index; word 0 sums to the ray count; per mode the wave sum of ray_w selected by end
+    code is the row's p_res, p_wall, w_left; words 14 and 15 are zero; the report's scales are free_map.scales'."""
+    ct, modes, n, ms, seed, x0, w = parity_inputs(name)
+    eng = fp_engine(ct, seed=99)
+    grid = FD.grid_from_bounds(bounds(ct), GRIDS[name])
+    got = map_call(eng, ct, modes, w, grid, n=n, max_segments=ms, x0=x0, seed=seed, rays=True)
+    eng.close()
+    assert_cells_are_the_rule(got, w, grid, ct, FC.lifetimes(ct))
+    # the same call without the per-ray outputs: the same cells
+    eng = fp_engine(ct, seed=99)
+    bare = map_call(eng, ct, modes, w, grid, n=n, max_segments=ms, x0=x0, seed=seed, rays=False)
+    eng.close()
+    assert bare['cells'].tobytes() == got['cells'].tobytes() and 'ray_cell' not in bare
+
+
+def test_clamping():
+    """A grid over the lower half of the box in x and y: the rays that start outside are clamped into the edge cells and counted."""
+    ct = FC.case('ttp')
+    modes = FC.spread_modes(ct, 32)
+    w = case_weights(ct, modes)[1]
+    x0 = FC.uniform_points(ct, 32, 64, 3)
+    b = bounds(ct)
+    n = (4, 3, 2)
+    lo, h = b[0].copy(), (b[1] - b[0]) / np.array([8.0, 6.0, 2.0])
+    grid = (lo, h, n)
+    eng = fp_engine(ct)
+    got = map_call(eng, ct, modes, w, grid, n=64, x0=x0, seed=5, rays=True)
+    eng.close()
+    _, out = FD.cell_index(x0.reshape(-1, 3), lo, h, n)
+    assert got['report']['clamped'] == int(out.sum()) and 0.6 < out.mean() < 0.9
+    assert_cells_are_the_rule(got, w, grid, ct, FC.lifetimes(ct))
+    inner = got['cells'][:-1, :-1, :, 0]
+    assert got['cells'][-1, -1, :, 0].sum() > 4 * inner.mean() * 2                  # the far corner column holds a quarter of the box
+
+
+def test_order_and_list_independence():
+    """The same call twice gives identical bytes; with capacity and weight_bound pinned cells(A) + cells(B) == cells(A u B) for
+    two disjoint 50-mode lists; the device sampler gives the same cells for a list and for its reverse."""
+    ct = FC.case('ttrrp_k')
+    act = FC.active_modes(ct)
+    pick = np.random.default_rng(8).choice(act.size, 100, replace=False)
+    A, B = act[np.sort(pick[:50])].astype(np.int32), act[np.sort(pick[50:])].astype(np.int32)
+    AB = np.concatenate([A, B])
+    wA, wB, wAB = (case_weights(ct, m)[1] for m in (A, B, AB))
+    grid = FD.grid_from_bounds(bounds(ct), (4, 3, 2))
+    eng = fp_engine(ct, seed=77)
+    pin = dict(capacity=100 * 70, weight_bound=float(np.abs(wAB).max()))
+    a1 = map_call(eng, ct, AB, wAB, grid, n=70, rays=False, **pin)
+    a2 = map_call(eng, ct, AB, wAB, grid, n=70, rays=False, **pin)
+    assert a1['cells'].tobytes() == a2['cells'].tobytes()
+    ca = map_call(eng, ct, A, wA, grid, n=70, rays=False, **pin)
+    cb = map_call(eng, ct, B, wB, grid, n=70, rays=False, **pin)
+    for k in ('k_K', 'k_P', 'k_T'):
+        assert ca['report'][k] == cb['report'][k] == a1['report'][k], k
+    assert np.array_equal(ca['cells'] + cb['cells'], a1['cells'])
+    rev = map_call(eng, ct, AB[::-1].copy(), wAB[::-1].copy(), grid, n=70, rays=False, **pin)
+    assert rev['cells'].tobytes() == a1['cells'].tobytes()
+    for k in MODE_KEYS:
+        assert rev[k][::-1].tobytes() == a1[k].tobytes(), k
+    # unpinned, the scales follow the call's own rays and weights
+    free = map_call(eng, ct, A, wA, grid, n=70, rays=False)
+    assert free['report']['k_P'] == a1['report']['k_P'] + 1 and free['report']['k_K'] >= a1['report']['k_K']
+    eng.close()
+
+
+def ttp_all():
+    """'ttp', every active mode (4368), n = 64, start points drawn on the device, grid 8 x 1 x 1, per-ray outputs (shared)."""
+    def make():
+        ct = FC.case('ttp')
+        modes = FC.active_modes(ct)
+        C, w = case_weights(ct, modes)
+        grid = FD.grid_from_bounds(bounds(ct), (8, 1, 1))
+        eng = fp_engine(ct, seed=1234)
+        got = map_call(eng, ct, modes, w, grid, n=64, rays=True)
+        eng.close()
+        return ct, modes, C, w, grid, got
+    return FC.cached(('free_map', 'ttp_all'), make)
+
+
+def test_sum_identity():
+    """For every a, b: |sum_c word(1 + 3a + b) 2^-k_K - sum_l w_la D_lb| <= rays 2^-(k_K + 1) + rays 2^-53 sum |terms|: the
+    rounding of the integers and the host's float sum, both derived."""
+    ct, modes, C, w, grid, got = ttp_all()
+    assert modes.size == 4368
+    rays, kK = got['report']['rays'], got['report']['k_K']
+    for a in range(3):
+        for b in range(3):
+            terms = w[:, None, a] * got['ray_D'][:, :, b]
+            word = int(got['cells'][..., 1 + 3 * a + b].sum())                     # (exact: |sum| < 2^62)
+            dev = abs(np.ldexp(float(word), -kK) - terms.sum())
+            bound = rays * 2.0 ** -(kK + 1) + rays * 2.0 ** -53 * np.abs(terms).sum()
+            print('w_%d D_%d: sum %.6e, deviation %.3e, bound %.3e' % (a, b, terms.sum(), dev, bound))
+            assert dev <= bound, (a, b)
+    # the flight time and the weights likewise
+    kT, kP = got['report']['k_T'], got['report']['k_P']
+    assert abs(np.ldexp(float(got['cells'][..., 13].sum()), -kT) - got['ray_T'].sum()) <= rays * 2.0 ** -(kT + 1) + rays * 2.0 ** -53 * got['ray_T'].sum()
+    assert abs(np.ldexp(float(got['cells'][..., 10:13].sum()), -kP) - got['ray_w'].sum()) <= rays * 2.0 ** -(kP + 1) + rays * 2.0 ** -53 * got['ray_w'].sum()
+
+
+def test_physics_slab_profile():
+    """'ttp', all active modes, 8 slab cells: the normalised count and solid profiles agree with film_cell_suppression within 5
+    standard errors per cell (the errors from the per-ray terms of the same call; the reference rule alone is held to the same
+    bound on the CPU, tests/test_free_map_host.py); the profile is symmetric under x -> L - x within the same bound; solid and
+    count differ by less than those errors on this box, where every cell is full."""
+    ct, modes, C, w, grid, got = ttp_all()
+    lo, h, n = grid
+    tau = FC.lifetimes(ct)[modes]
+    kb = FP.bulk_kappa(C, FC.group_vel(ct)[modes], tau, ct['tables']['QV'])
+    cf, bulk = closed_form_profile(ct, modes, w, 8)
+    full = np.ones(n)
+    prof, err = {}, {}
+    for kind in FM.KINDS:
+        m = FM.normalise(got['cells'], got['report'], 64, modes.size, kind, solid_fraction=full, cell_volume=float(np.prod(h)), kappa_bulk=kb)
+        val, se = profile_with_errors(got['ray_x0'], got['ray_D'], w, lo, h, n, kind, cell_fraction=full / 8.0)
+        assert np.allclose(m['kappa'][..., 0, 0], FP._unit() * val, rtol=1e-9, atol=0)
+        prof[kind], err[kind] = m['suppression'][:, 0, 0], se[:, 0, 0] / bulk
+        z = np.abs(prof[kind] - cf) / err[kind]
+        print('%s: suppression %s\n  closed form %s\n  deviations in s.e. %s' % (kind, np.round(prof[kind], 5), np.round(cf, 5), np.round(z, 2)))
+        assert z.max() <= 5.0, (kind, z)
+        sym = np.abs(prof[kind] - prof[kind][::-1]) / np.sqrt(err[kind] ** 2 + err[kind][::-1] ** 2)
+        assert sym.max() <= 5.0, (kind, sym)
+        assert np.all(m['p_wall'] == 0) and np.all(m['p_res'][[0, -1]] > m['p_res'][[3, 4]])
+    assert np.all(np.abs(prof['solid'] - prof['count']) <= 5.0 * err['solid'])
+    assert cf[0] < cf[3] and prof['count'][0] < prof['count'][3]                       # the dead layer next to the walls
+    # 'solid' sums back to the global tensor of the same rays
+    glob = FP.kappa_tensor(C, FC.group_vel(ct)[modes], got['D'] / 64.0, ct['tables']['QV'])
+    m = FM.normalise(got['cells'], got['report'], 64, modes.size, 'solid', solid_fraction=full, cell_volume=float(np.prod(h)))
+    assert np.allclose(FM.solid_mean(m['kappa'], full), glob, rtol=1e-9, atol=1e-9 * glob[0, 0])
+
+
+def test_does_not_interfere():
+    """20 steps with a free_path_map call after step 10 against 20 without: the same history rows and particles (the rule of
+    tests/test_gpu_free_path.py); free_paths_info() is unchanged by the map call; a field configured with set_field reads the
+    same after the map call as before."""
+    from util import make_engine, random_population
+    from test_gpu_replicas import assert_same_rows, assert_same_particles
+    ct = FC.case('ttp')
+    pos, mode, occ, counter = random_population(ct, 30000, seed=5)
+    modes = FC.spread_modes(ct, 40)
+    w = case_weights(ct, modes)[1]
+    fgrid = FD.grid_from_bounds(bounds(ct), (5, 2, 2))
+    engs, rows = [], []
+    for with_call in (False, True):
+        eng = make_engine(ct, pos, mode, occ, counter, seed=42)
+        eng.set_field(fgrid[0], fgrid[1], fgrid[2], 10)
+        t0 = eng.step(10)
+        if with_call:
+            eng.free_paths(FC.lifetimes(ct), n=8, modes=modes[:4])
+            info, fld = eng.free_paths_info(), eng.field()
+            r = map_call(eng, ct, modes, w, FD.grid_from_bounds(bounds(ct), (4, 3, 2)), n=64, rays=False)
+            assert r['report']['rays'] == 40 * 64 and eng.get_step() == 10 and eng.free_path_map_info() == r['report']
+            assert eng.free_paths_info() == info and info['calls'] == 1
+            after = eng.field()
+            assert after['samples'] == fld['samples'] == 1 and all(np.array_equal(after[k], fld[k]) for k in ('N', 'E', 'F'))
+        t1 = eng.step(10)
+        engs.append(eng)
+        rows.append((t0, t1, eng.field()))
+    assert_same_rows(rows[1][0], rows[0][0], 'steps 1-10')
+    assert_same_rows(rows[1][1], rows[0][1], 'steps 11-20, after the call')
+    assert_same_particles(engs[1], engs[0], 'after 20 steps')
+    assert rows[1][2]['samples'] == rows[0][2]['samples'] == 2 and np.array_equal(rows[1][2]['N'], rows[0][2]['N'])
+    for e in engs:
+        e.close()
+
+
+def test_refusals():
+    """Every NK_ERR_ARG case returns its error with a text that names the cause and leaves free_path_map_info()'s calls and
+    bytes unchanged: argument checks made on the host before any launch."""
+    from nanokappa_amd.engine import Engine, NkError
+    ct = FC.case('ttp')
+    tau = FC.lifetimes(ct)
+    M = ct['M']
+    modes4 = np.arange(4, dtype=np.int32)
+    lo, h, n = FD.grid_from_bounds(bounds(ct), (4, 3, 2))
+
+    def refused(eng, text, **kw):
+        args = dict(tau=tau, weight=np.ones((4, 3)), lo=lo, h=h, n_cells=n, n=8, modes=modes4)
+        args.update(kw)
+        before = eng.free_path_map_info()
+        with pytest.raises(NkError, match=r'\(-2\)') as e:
+            eng.free_path_map(args.pop('tau'), args.pop('weight'), args.pop('lo'), args.pop('h'), args.pop('n_cells'), **args)
+        assert text in str(e.value), str(e.value)
+        after = eng.free_path_map_info()
+        assert after['calls'] == before['calls'] and after['bytes'] == before['bytes']
+
+    eng = Engine(0, 1)
+    refused(eng, 'no material')
+    eng.set_material(ct['tables'])
+    refused(eng, 'no mesh')
+    eng.close()
+    eng = fp_engine(ct)
+    zero = eng.free_path_map_info()
+    assert zero['calls'] == 0 and zero['bytes'] == 0 and zero['rays'] == 0
+    refused(eng, 'n_samples', n=0)
+    refused(eng, 'n_samples', n=-3)
+    refused(eng, 'out of range', modes=np.array([0, 1, 2, M], dtype=np.int32))
+    refused(eng, 'out of range', modes=np.array([-1, 0, 1, 2], dtype=np.int32))
+    refused(eng, 'tau is NULL', tau=None)
+    refused(eng, 'weight is NULL', weight=None)
+    bad = np.ones((4, 3))
+    bad[2, 1] = np.nan
+    refused(eng, 'not finite', weight=bad)
+    bad[2, 1] = np.inf
+    refused(eng, 'not finite', weight=bad)
+    refused(eng, 'cell counts', n_cells=(4, 0, 2))
+    refused(eng, 'cell counts', n_cells=(-1, 3, 2))
+    refused(eng, 'cell sizes', h=np.array([1.0, 0.0, 1.0]))
+    refused(eng, 'cell sizes', h=np.array([1.0, -2.0, 1.0]))
+    refused(eng, 'cell sizes', h=np.array([1.0, np.nan, 1.0]))
+    refused(eng, 'more than the grid takes', n_cells=(257, 256, 256))
+    refused(eng, 'must not be negative', capacity=-1)
+    # cells NULL: the binding always passes a buffer, so the C entry point is called directly
+    import ctypes as C
+    from nanokappa_amd import engine as E
+    a, g, rep = E.nk_free_path_args(), E.nk_free_path_grid(), E.nk_free_path_map_report()
+    wt = np.ones((4, 3))
+    a.n_modes, a.modes, a.n_samples, a.tau = 4, E._p(modes4, E.c_ip), 8, E._p(tau)
+    g.n[:], g.lo[:], g.h[:], g.weight = list(n), list(lo), list(h), E._p(wt)
+    rc = eng.L.nk_free_paths_map(eng.h, C.byref(a), C.byref(g), None, None, None, C.byref(rep))
+    assert rc == E.ERR_ARG and 'cells is NULL' in eng.L.nk_last_error(eng.h).decode()
+    assert rep.rays == 0 and rep.calls == 0 and rep.bytes == 0 and rep.k_K == 0 and rep.B_T == 0.0          # the report is all zero
+    assert eng.free_path_map_info() == zero                  # nothing ran
+    ok = eng.free_path_map(tau, np.ones((4, 3)), lo, h, n, n=8, modes=modes4)
+    assert ok['report']['calls'] == 1 and ok['report']['overflow'] == 0 and eng.free_paths_info()['calls'] == 0
+    eng.close()
+    eng = fp_engine(ct, volume=False)
+    refused(eng, 'volume tables')
+    eng.close()
+    cr = FC.case('ttrrp')
+    eng = fp_engine(cr, rough=False)
+    refused(eng, 'rough', tau=FC.lifetimes(cr))
+    eng.close()
+
+
+def _ttp_argv(particles, iterations, extra=()):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden'))
+    import ref_harness_args as A
+    return A.argv_for('ttp', particles, iterations) + ['--seed', '7'] + list(extra)
+
+
+def test_population_and_front_end(tmp_path):
+    """--free_path 64 --free_path_map 6 2 2 solid on 'ttp' writes free_path_map.npz and free_path_map.vtk before the first step;
+    kappa summed with the solid weights is k_free_path.txt's tensor of the same rays; solid_fraction is 1 everywhere;
+    Population.free_path_map returns the same; without the option nothing is launched or allocated."""
+    from nanokappa_amd import nanokappa
+
+    def run(name, extra):
+        pf = tmp_path / (name + '.txt')
+        pf.write_text(' '.join(_ttp_argv(20000, 10, ['--results_folder', str(tmp_path / name)] + extra)))
+        cwd = os.getcwd()
+        os.chdir(str(tmp_path))
+        try:
+            return nanokappa.main(['-ff', str(pf)])
+        finally:
+            sys.stdout = sys.__stdout__
+            os.chdir(cwd)
+
+    pop = run('with', ['--free_path', '64', '--free_path_map', '6', '2', '2', 'solid'])
+    folder = pop.results_folder_name
+    z = FM.read_free_path_map_npz(FM.free_path_map_npz_path(folder))
+    v = FM.read_free_path_map_vtk(FM.free_path_map_vtk_path(folder))
+    m = pop.free_path_map_last
+    assert z['n'] == (6, 2, 2) and z['kind'] == 'solid' and z['axis'] == 0 and z['n_samples'] == 64 and z['T'] == 300.0
+    assert z['report']['overflow'] == 0 and z['report']['clamped'] == 0 and z['report']['calls'] == 1 and z['report'] == m['report']
+    assert np.array_equal(z['cells'], m['cells']) and np.array_equal(z['kappa'], m['kappa']) and z['cells'].shape == (6, 2, 2, 16)
+    assert v['n'] == (6, 2, 2) and np.array_equal(v['kappa'], m['kappa'][..., 0, 0]) and np.array_equal(v['suppression'], m['suppression'])
+    assert np.array_equal(v['N'], m['N']) and m['N'].sum() == z['report']['rays'] == z['n_list'] * 64
+    # solid_fraction is 1 everywhere: the box fills its bounding box (the exact volumes, to their rounding)
+    assert np.allclose(z['solid_fraction'], 1.0, rtol=0, atol=1e-12) and np.array_equal(v['solid_fraction'], z['solid_fraction'])
+    # kappa summed with the solid weights against k_free_path.txt's tensor (the free_paths call of the same run: the same rays):
+    # the bound of the sum identity -- the integers' rounding and a float sum of the terms, each at most B_K -- times unit / n
+    txt = FP.read_k_free_path(FP.k_free_path_path(folder))
+    rays, kK, BK = z['report']['rays'], z['report']['k_K'], z['report']['B_K']
+    bound = FP._unit() / 64.0 * (rays * 2.0 ** -(kK + 1) + rays * 2.0 ** -53 * rays * BK)
+    tot = FM.solid_mean(z['kappa'], z['solid_fraction'])
+    slack = 64 * 2.0 ** -53 * np.abs(txt['kappa']).max()             # the 24 products and sums of solid_mean itself
+    print('kappa from the map %s\nfrom k_free_path.txt %s\nbound %.3e' % (tot.ravel(), txt['kappa'].ravel(), bound + slack))
+    assert np.all(np.abs(tot - txt['kappa']) <= bound + slack)
+    assert np.array_equal(z['kappa_global'], txt['kappa']) and np.array_equal(z['kappa_bulk'], txt['kappa_bulk'])
+    assert np.array_equal(m['summary']['kappa'], txt['kappa'])
+    sup = m['suppression'][:, 0, 0]
+    assert sup[0] < sup[2] and sup[-1] < sup[3] and 0.0 < sup.min() and sup.max() < 0.1
+    # Population.free_path_map with its own arguments: another grid and temperature, a mode list, count, no files
+    before = os.path.getmtime(FM.free_path_map_npz_path(folder))
+    t = pop.free_path_map((3, 1, 1), n=16, T=250.0, modes=m['summary']['modes'][:30], normalise='count', write=False)
+    assert t['T'] == 250.0 and t['kappa'].shape == (3, 1, 1, 3, 3) and t['report']['calls'] == 2 and t['solid_fraction'] is None
+    assert t['N'].sum() == 30 * 16 and os.path.getmtime(FM.free_path_map_npz_path(folder)) == before
+    assert pop.current_timestep == 10
+    pop.engine.close()
+
+    pop = run('without', ['--free_path', '64'])
+    folder = pop.results_folder_name
+    assert not os.path.exists(FM.free_path_map_npz_path(folder)) and not os.path.exists(FM.free_path_map_vtk_path(folder))
+    rep = pop.engine.free_path_map_info()
+    assert rep['calls'] == 0 and rep['bytes'] == 0 and rep['rays'] == 0
+    pop.engine.close()
