@@ -24,7 +24,6 @@
 #include "nk_group.h"
 #include "nk_freepath.h"
 #include "nk_freecols.h"
-#include "nk_freemap.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -146,10 +145,10 @@ struct nk_ctx {
     // mode-resolved tally (nk_set_modes, k_modes; nk_modes.hip): off by default -- then nothing is launched or allocated
     NkModesHost modes;
     double res_T_max = 0.0;              // highest reservoir temperature (nk_set_reservoirs): bounds the field's terms
-    // free-path sampling (nk_free_paths, k_free_paths; nk_freepath.hip): the last call's report -- nothing is kept on the device
+    // free-path sampling (nk_free_paths, k_free_paths<*, false>; nk_freepath.hip): the last call's report -- nothing is kept on the device
     nk_free_path_report fp_last = {};
     int32_t fc_calls = 0;        // nk_free_paths_columns calls so far (k_free_columns; nk_freecols.hip)
-    nk_free_path_map_report fm_last = {};   // the last nk_free_paths_map call's report (k_free_map; nk_freemap.hip)
+    nk_free_path_map_report fm_last = {};   // the last nk_free_paths_map call's report (k_free_paths<*, true>; nk_freepath.hip)
 };
 
 #define NK_HIP(call)                                                                                   \
@@ -3887,96 +3886,145 @@ int nk_build_enter_prob(nk_ctx *ctx, int32_t R, const double *normal_in, const d
 }
 
 // ------------------------------------------------------------------------------------- free-path sampling
+// What nk_free_paths, nk_free_paths_columns and nk_free_paths_map share.  A call weighs its rays with K lifetime tables: K = 1
+// for the plain call and the map, the leading axis of tau, of the rows and of the per-ray outputs (but x0) for the columns.
+
+// The refusals, in the words of the entry point `who`; tau_holds: what its message says a->tau is.  Sets the list's length and
+// the ray count.
+static int nk_free_refuse(nk_ctx *ctx, const std::string &who, const nk_free_path_args *a, const char *tau_holds, int64_t &nlist, int64_t &rays) {
+    NK_ARG(ctx->have_material, who + ": no material (nk_set_material first)");
+    NK_ARG(ctx->have_mesh, who + ": no mesh (nk_set_mesh first)");
+    const NkDev &d = ctx->d;
+    NK_ARG(a->tau, who + ": tau is NULL (" + tau_holds + ")");
+    NK_ARG(a->n_samples > 0, who + ": n_samples = " + std::to_string(a->n_samples) + " must be positive");
+    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, who + ": max_segments and w_min must not be negative");
+    nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
+    NK_ARG(nlist >= 0, who + ": n_modes must not be negative");
+    if (a->modes)
+        for (int64_t i = 0; i < nlist; ++i)
+            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, who + ": mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
+                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
+    for (int fc = 0; fc < d.Fc; ++fc)
+        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
+               who + ": facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
+    NK_ARG(a->x0 || d.nS > 0, who + ": no start points (x0) and the mesh was set without its volume tables (simplices)");
+    rays = nlist * (int64_t)a->n_samples;
+    NK_ARG(rays < (1ll << 31), who + ": " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    return NK_OK;
+}
+
+// The buffers of a call -- everything nk_free_path_args and nk_free_path_rays imply --, freed on every return path.
+struct NkFreeCall {
+    const nk_free_path_args *a;
+    const nk_free_path_rays *pr;     // null when no per-ray output is asked for
+    int64_t K, M, nlist, rays;
+    NkDevBuf<int32_t> modes;
+    NkDevBuf<double> tau, x0, rows;
+    NkDevBuf<unsigned long long> cnt;
+    NkDevBuf<double> rD, rT, rx;
+    NkDevBuf<int32_t> rs, re;
+    NkFreeCall(const nk_ctx *ctx, const nk_free_path_args *a_, const nk_free_path_rays *p, int64_t K_, int64_t nlist_, int64_t rays_)
+        : a(a_), pr(p && (p->D || p->T || p->segments || p->end || p->x0) ? p : nullptr), K(K_), M(ctx->d.M), nlist(nlist_), rays(rays_),
+          modes(a->modes, a->modes ? nlist : 0), tau(a->tau, K * M), x0(a->x0, a->x0 ? rays * 3 : 0),
+          rows(nullptr, K * nlist * NK_FP_ROW), cnt(nullptr, K * nlist * NK_FP_CNT),
+          rD(nullptr, (pr && pr->D) ? K * rays * 3 : 0), rT(nullptr, (pr && pr->T) ? K * rays : 0), rx(nullptr, (pr && pr->x0) ? rays * 3 : 0),
+          rs(nullptr, (pr && pr->segments) ? K * rays : 0), re(nullptr, (pr && pr->end) ? K * rays : 0) {}
+    hipError_t err() const {
+        for (hipError_t e : {modes.err, tau.err, x0.err, rows.err, cnt.err, rD.err, rT.err, rx.err, rs.err, re.err})
+            if (e != hipSuccess) return e;
+        return hipSuccess;
+    }
+    // the kernels' record, with the defaults of the arguments
+    NkFreeDev dev(const nk_ctx *ctx) const {
+        NkFreeDev f;
+        f.modes = a->modes ? modes.p : nullptr;
+        f.nlist = (int32_t)nlist; f.n = a->n_samples;
+        f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
+        f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
+        f.tau = tau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? x0.p : nullptr;
+        f.seed = a->seed ? a->seed : ctx->d.seed;
+        f.rows = rows.p; f.counts = cnt.p;
+        f.ray_D = (pr && pr->D) ? rD.p : nullptr; f.ray_T = (pr && pr->T) ? rT.p : nullptr;
+        f.ray_x0 = (pr && pr->x0) ? rx.p : nullptr;
+        f.ray_seg = (pr && pr->segments) ? rs.p : nullptr; f.ray_end = (pr && pr->end) ? re.p : nullptr;
+        return f;
+    }
+    // bytes of these buffers as the reports count them
+    int64_t bytes() const {
+        return (a->modes ? nlist * 4 : 0) + K * M * 8 + (a->x0 ? rays * 24 : 0) + K * nlist * (NK_FP_ROW + NK_FP_CNT) * 8 +
+               ((pr && pr->D) ? K * rays * 24 : 0) + ((pr && pr->T) ? K * rays * 8 : 0) + ((pr && pr->x0) ? rays * 24 : 0) +
+               ((pr && pr->segments) ? K * rays * 4 : 0) + ((pr && pr->end) ? K * rays * 4 : 0);
+    }
+    // the rows into pm (with the column axis), the counts into casts, missed, capped [K], the per-ray outputs into pr
+    int copy_out(nk_ctx *ctx, const nk_free_path_modes *pm, int64_t *casts, int64_t *missed, int64_t *capped) const {
+        std::vector<double> hrows((size_t)(K * nlist) * NK_FP_ROW);
+        std::vector<unsigned long long> hcnt((size_t)(K * nlist) * NK_FP_CNT);
+        NK_HIP(rows.get(hrows.data(), K * nlist * NK_FP_ROW));
+        NK_HIP(cnt.get(hcnt.data(), K * nlist * NK_FP_CNT));
+        for (int64_t c = 0; c < K; ++c)
+            for (int64_t i = 0; i < nlist; ++i) {
+                const int64_t ci = c * nlist + i;
+                const double *w = &hrows[(size_t)ci * NK_FP_ROW];
+                if (pm) {
+                    for (int x = 0; x < 3; ++x) { if (pm->D) pm->D[3 * ci + x] = w[x]; if (pm->D2) pm->D2[3 * ci + x] = w[3 + x]; }
+                    if (pm->T) pm->T[ci] = w[6];
+                    if (pm->hits) pm->hits[ci] = w[7];
+                    if (pm->p_res) pm->p_res[ci] = w[8];
+                    if (pm->p_wall) pm->p_wall[ci] = w[9];
+                    if (pm->w_left) pm->w_left[ci] = w[10];
+                    if (pm->p_int) pm->p_int[ci] = w[11];
+                }
+                casts[c] += (int64_t)hcnt[(size_t)ci * NK_FP_CNT]; missed[c] += (int64_t)hcnt[(size_t)ci * NK_FP_CNT + 1];
+                capped[c] += (int64_t)hcnt[(size_t)ci * NK_FP_CNT + 2];
+            }
+        if (pr) {
+            if (pr->D) NK_HIP(rD.get(pr->D, K * rays * 3));
+            if (pr->T) NK_HIP(rT.get(pr->T, K * rays));
+            if (pr->x0) NK_HIP(rx.get(pr->x0, rays * 3));
+            if (pr->segments) NK_HIP(rs.get(pr->segments, K * rays));
+            if (pr->end) NK_HIP(re.get(pr->end, K * rays));
+        }
+        return NK_OK;
+    }
+};
+
+// launch() between two events on the stream, waited for: the device seconds of what it launched
+template <class Launch>
+static hipError_t nk_free_timed(hipStream_t stream, double &seconds, Launch launch) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, stream);
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(e1, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    seconds = 1e-3 * (double)ms;
+    return e;
+}
+
 // k_free_paths (nk_freepath.hip) on buffers of this call alone: the particle store, its counters, the step counter and the
 // emission bookkeeping are neither read nor written.
 int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_path_modes *pm, const nk_free_path_rays *pr, nk_free_path_report *rep) {
     if (rep) memset(rep, 0, sizeof(*rep));
     NK_ARG(ctx && a, "nk_free_paths: NULL argument");
-    NK_ARG(ctx->have_material, "nk_free_paths: no material (nk_set_material first)");
-    NK_ARG(ctx->have_mesh, "nk_free_paths: no mesh (nk_set_mesh first)");
-    NkDev &d = ctx->d;
-    NK_ARG(a->tau, "nk_free_paths: tau is NULL (the lifetimes of all Q*J modes at the temperature of the estimate)");
-    NK_ARG(a->n_samples > 0, "nk_free_paths: n_samples = " + std::to_string(a->n_samples) + " must be positive");
-    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, "nk_free_paths: max_segments and w_min must not be negative");
-    const int64_t nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
-    NK_ARG(nlist >= 0, "nk_free_paths: n_modes must not be negative");
-    if (a->modes)
-        for (int64_t i = 0; i < nlist; ++i)
-            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, "nk_free_paths: mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
-                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
-    for (int fc = 0; fc < d.Fc; ++fc)
-        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
-               "nk_free_paths: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
-    NK_ARG(a->x0 || d.nS > 0, "nk_free_paths: no start points (x0) and the mesh was set without its volume tables (simplices)");
-    const int64_t rays = nlist * (int64_t)a->n_samples;
-    NK_ARG(rays < (1ll << 31), "nk_free_paths: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    int64_t nlist, rays;
+    NK_TRY(nk_free_refuse(ctx, "nk_free_paths", a, "the lifetimes of all Q*J modes at the temperature of the estimate", nlist, rays));
     NK_HIP(hipSetDevice(ctx->device));
-    const bool want_rays = pr && (pr->D || pr->T || pr->segments || pr->end || pr->x0);
-    NK_BUF(int32_t, dmodes, a->modes, a->modes ? nlist : 0);
-    NK_BUF(double, dtau, a->tau, d.M);
-    NK_BUF(double, dx0, a->x0, a->x0 ? rays * 3 : 0);
-    NK_BUF(double, drows, nullptr, nlist * NK_FP_ROW);
-    NK_BUF(unsigned long long, dcnt, nullptr, nlist * NK_FP_CNT);
-    NK_BUF(double, drD, nullptr, (want_rays && pr->D) ? rays * 3 : 0);
-    NK_BUF(double, drT, nullptr, (want_rays && pr->T) ? rays : 0);
-    NK_BUF(double, drx, nullptr, (want_rays && pr->x0) ? rays * 3 : 0);
-    NK_BUF(int32_t, drs, nullptr, (want_rays && pr->segments) ? rays : 0);
-    NK_BUF(int32_t, dre, nullptr, (want_rays && pr->end) ? rays : 0);
-    NkFreeDev f;
-    f.modes = a->modes ? dmodes.p : nullptr;
-    f.nlist = (int32_t)nlist; f.n = a->n_samples;
-    f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
-    f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
-    f.tau = dtau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? dx0.p : nullptr;
-    f.seed = a->seed ? a->seed : d.seed;
-    f.rows = drows.p; f.counts = dcnt.p;
-    f.ray_D = (want_rays && pr->D) ? drD.p : nullptr; f.ray_T = (want_rays && pr->T) ? drT.p : nullptr;
-    f.ray_x0 = (want_rays && pr->x0) ? drx.p : nullptr;
-    f.ray_seg = (want_rays && pr->segments) ? drs.p : nullptr; f.ray_end = (want_rays && pr->end) ? dre.p : nullptr;
+    NkFreeCall call(ctx, a, pr, 1, nlist, rays);
+    NK_HIP(call.err());
+    const NkFreeDev f = call.dev(ctx);
     nk_free_path_report r;
     memset(&r, 0, sizeof(r));
     r.rays = rays;
     r.geometry_mode = nk_geom_mode(ctx);
     r.calls = ctx->fp_last.calls + 1;
-    r.bytes = (a->modes ? nlist * 4 : 0) + (int64_t)d.M * 8 + (a->x0 ? rays * 24 : 0) + nlist * (NK_FP_ROW + NK_FP_CNT) * 8 +
-              (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) + (f.ray_x0 ? rays * 24 : 0) + (f.ray_seg ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) e = nk_free_paths_launch(d, f, r.geometry_mode, nk_lds(ctx, true), ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    NK_HIP(e);
-    r.seconds = 1e-3 * (double)ms;
-    std::vector<double> rows((size_t)nlist * NK_FP_ROW);
-    std::vector<unsigned long long> cnt((size_t)nlist * NK_FP_CNT);
-    NK_HIP(drows.get(rows.data(), nlist * NK_FP_ROW));
-    NK_HIP(dcnt.get(cnt.data(), nlist * NK_FP_CNT));
-    for (int64_t i = 0; i < nlist; ++i) {
-        const double *w = &rows[(size_t)i * NK_FP_ROW];
-        if (pm) {
-            for (int c = 0; c < 3; ++c) { if (pm->D) pm->D[3 * i + c] = w[c]; if (pm->D2) pm->D2[3 * i + c] = w[3 + c]; }
-            if (pm->T) pm->T[i] = w[6];
-            if (pm->hits) pm->hits[i] = w[7];
-            if (pm->p_res) pm->p_res[i] = w[8];
-            if (pm->p_wall) pm->p_wall[i] = w[9];
-            if (pm->w_left) pm->w_left[i] = w[10];
-            if (pm->p_int) pm->p_int[i] = w[11];
-        }
-        r.casts += (int64_t)cnt[(size_t)i * NK_FP_CNT]; r.missed += (int64_t)cnt[(size_t)i * NK_FP_CNT + 1]; r.capped += (int64_t)cnt[(size_t)i * NK_FP_CNT + 2];
-    }
-    if (want_rays) {
-        if (pr->D) NK_HIP(drD.get(pr->D, rays * 3));
-        if (pr->T) NK_HIP(drT.get(pr->T, rays));
-        if (pr->x0) NK_HIP(drx.get(pr->x0, rays * 3));
-        if (pr->segments) NK_HIP(drs.get(pr->segments, rays));
-        if (pr->end) NK_HIP(dre.get(pr->end, rays));
-    }
+    r.bytes = call.bytes();
+    NK_HIP(nk_free_timed(ctx->stream, r.seconds, [&] { return nk_free_paths_launch(ctx->d, f, nullptr, r.geometry_mode, nk_lds(ctx, true), ctx->stream); }));
+    NK_TRY(call.copy_out(ctx, pm, &r.casts, &r.missed, &r.capped));
     ctx->fp_last = r;
     if (rep) *rep = r;
     return NK_OK;
@@ -3995,140 +4043,55 @@ int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *a, int32_t n_col
     NK_ARG(ctx && a, "nk_free_paths_columns: NULL argument");
     NK_ARG(n_columns >= 1 && n_columns <= NK_FREE_PATH_MAX_COLUMNS, "nk_free_paths_columns: n_columns = " + std::to_string(n_columns) +
                                                                         " must be 1 .. " + std::to_string(NK_FREE_PATH_MAX_COLUMNS));
-    NK_ARG(ctx->have_material, "nk_free_paths_columns: no material (nk_set_material first)");
-    NK_ARG(ctx->have_mesh, "nk_free_paths_columns: no mesh (nk_set_mesh first)");
-    NkDev &d = ctx->d;
-    NK_ARG(a->tau, "nk_free_paths_columns: tau is NULL (per column the lifetimes of all Q*J modes)");
-    NK_ARG(a->n_samples > 0, "nk_free_paths_columns: n_samples = " + std::to_string(a->n_samples) + " must be positive");
-    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, "nk_free_paths_columns: max_segments and w_min must not be negative");
-    const int64_t nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
-    NK_ARG(nlist >= 0, "nk_free_paths_columns: n_modes must not be negative");
-    if (a->modes)
-        for (int64_t i = 0; i < nlist; ++i)
-            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, "nk_free_paths_columns: mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
-                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
-    for (int fc = 0; fc < d.Fc; ++fc)
-        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
-               "nk_free_paths_columns: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
-    NK_ARG(a->x0 || d.nS > 0, "nk_free_paths_columns: no start points (x0) and the mesh was set without its volume tables (simplices)");
-    const int64_t rays = nlist * (int64_t)a->n_samples;
-    NK_ARG(rays < (1ll << 31), "nk_free_paths_columns: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    int64_t nlist, rays;
+    NK_TRY(nk_free_refuse(ctx, "nk_free_paths_columns", a, "per column the lifetimes of all Q*J modes", nlist, rays));
     NK_HIP(hipSetDevice(ctx->device));
     const int64_t K = n_columns;
     const int ntiles = (int)((K + NK_FC_TILE - 1) / NK_FC_TILE);
     const unsigned grid = nk_free_columns_grid(nlist, a->n_samples);
     const int64_t nacc = a->n_samples > 64 ? (int64_t)grid * NK_FP_WAVES * (K < NK_FC_TILE ? K : NK_FC_TILE) * NK_FC_ACC * 64 : 0;
-    const bool want_rays = pr && (pr->D || pr->T || pr->segments || pr->end || pr->x0);
-    NK_BUF(int32_t, dmodes, a->modes, a->modes ? nlist : 0);
-    NK_BUF(double, dtau, a->tau, K * d.M);
-    NK_BUF(double, dx0, a->x0, a->x0 ? rays * 3 : 0);
-    NK_BUF(double, drows, nullptr, K * nlist * NK_FP_ROW);
-    NK_BUF(unsigned long long, dcnt, nullptr, K * nlist * NK_FP_CNT);
+    NkFreeCall call(ctx, a, pr, K, nlist, rays);
+    NK_HIP(call.err());
     NK_BUF(unsigned long long, dshared, nullptr, (int64_t)ntiles * nlist);
     NK_BUF(double, dacc, nullptr, nacc);
-    NK_BUF(double, drD, nullptr, (want_rays && pr->D) ? K * rays * 3 : 0);
-    NK_BUF(double, drT, nullptr, (want_rays && pr->T) ? K * rays : 0);
-    NK_BUF(double, drx, nullptr, (want_rays && pr->x0) ? rays * 3 : 0);
-    NK_BUF(int32_t, drs, nullptr, (want_rays && pr->segments) ? K * rays : 0);
-    NK_BUF(int32_t, dre, nullptr, (want_rays && pr->end) ? K * rays : 0);
     NkFreeColsDev q;
-    NkFreeDev &f = q.f;
-    f.modes = a->modes ? dmodes.p : nullptr;
-    f.nlist = (int32_t)nlist; f.n = a->n_samples;
-    f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
-    f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
-    f.tau = dtau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? dx0.p : nullptr;
-    f.seed = a->seed ? a->seed : d.seed;
-    f.rows = drows.p; f.counts = dcnt.p;
-    f.ray_D = (want_rays && pr->D) ? drD.p : nullptr; f.ray_T = (want_rays && pr->T) ? drT.p : nullptr;
-    f.ray_x0 = (want_rays && pr->x0) ? drx.p : nullptr;
-    f.ray_seg = (want_rays && pr->segments) ? drs.p : nullptr; f.ray_end = (want_rays && pr->end) ? dre.p : nullptr;
-    q.M = d.M; q.rays = rays; q.acc = nacc ? dacc.p : nullptr;
+    q.f = call.dev(ctx);
+    q.M = ctx->d.M; q.rays = rays; q.acc = nacc ? dacc.p : nullptr;
     nk_free_path_columns_report r;
     memset(&r, 0, sizeof(r));
     r.rays = rays;
     r.n_columns = n_columns; r.tile = NK_FC_TILE; r.launches = nlist > 0 ? ntiles : 0;
     r.geometry_mode = nk_geom_mode(ctx);
     r.calls = ctx->fc_calls + 1;
-    r.bytes = (a->modes ? nlist * 4 : 0) + K * (int64_t)d.M * 8 + (a->x0 ? rays * 24 : 0) + K * nlist * (NK_FP_ROW + NK_FP_CNT) * 8 + (int64_t)ntiles * nlist * 8 +
-              nacc * 8 + (f.ray_D ? K * rays * 24 : 0) + (f.ray_T ? K * rays * 8 : 0) + (f.ray_x0 ? rays * 24 : 0) + (f.ray_seg ? K * rays * 4 : 0) +
-              (f.ray_end ? K * rays * 4 : 0);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    for (int t = 0; t < ntiles && e == hipSuccess; ++t) {
-        q.c0 = t * NK_FC_TILE;
-        q.kc = (int32_t)(K - q.c0 < NK_FC_TILE ? K - q.c0 : NK_FC_TILE);
-        q.shared = dshared.p + (int64_t)t * nlist;
-        e = nk_free_columns_launch(d, q, r.geometry_mode, nk_lds(ctx, true), grid, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    NK_HIP(e);
-    r.seconds = 1e-3 * (double)ms;
-    std::vector<double> rows((size_t)(K * nlist) * NK_FP_ROW);
-    std::vector<unsigned long long> cnt((size_t)(K * nlist) * NK_FP_CNT), shared((size_t)ntiles * nlist);
-    NK_HIP(drows.get(rows.data(), K * nlist * NK_FP_ROW));
-    NK_HIP(dcnt.get(cnt.data(), K * nlist * NK_FP_CNT));
+    r.bytes = call.bytes() + (int64_t)ntiles * nlist * 8 + nacc * 8;
+    NK_HIP(nk_free_timed(ctx->stream, r.seconds, [&] {
+        hipError_t e = hipSuccess;
+        for (int t = 0; t < ntiles && e == hipSuccess; ++t) {
+            q.c0 = t * NK_FC_TILE;
+            q.kc = (int32_t)(K - q.c0 < NK_FC_TILE ? K - q.c0 : NK_FC_TILE);
+            q.shared = dshared.p + (int64_t)t * nlist;
+            e = nk_free_columns_launch(ctx->d, q, r.geometry_mode, nk_lds(ctx, true), grid, ctx->stream);
+        }
+        return e;
+    }));
+    std::vector<unsigned long long> shared((size_t)ntiles * nlist);
     NK_HIP(dshared.get(shared.data(), (int64_t)ntiles * nlist));
     for (unsigned long long v : shared) r.casts_shared += (int64_t)v;
-    for (int64_t c = 0; c < K; ++c)
-        for (int64_t i = 0; i < nlist; ++i) {
-            const int64_t ci = c * nlist + i;
-            const double *w = &rows[(size_t)ci * NK_FP_ROW];
-            if (pm) {
-                for (int x = 0; x < 3; ++x) { if (pm->D) pm->D[3 * ci + x] = w[x]; if (pm->D2) pm->D2[3 * ci + x] = w[3 + x]; }
-                if (pm->T) pm->T[ci] = w[6];
-                if (pm->hits) pm->hits[ci] = w[7];
-                if (pm->p_res) pm->p_res[ci] = w[8];
-                if (pm->p_wall) pm->p_wall[ci] = w[9];
-                if (pm->w_left) pm->w_left[ci] = w[10];
-                if (pm->p_int) pm->p_int[ci] = w[11];
-            }
-            r.casts[c] += (int64_t)cnt[(size_t)ci * NK_FP_CNT]; r.missed[c] += (int64_t)cnt[(size_t)ci * NK_FP_CNT + 1];
-            r.capped[c] += (int64_t)cnt[(size_t)ci * NK_FP_CNT + 2];
-        }
-    if (want_rays) {
-        if (pr->D) NK_HIP(drD.get(pr->D, K * rays * 3));
-        if (pr->T) NK_HIP(drT.get(pr->T, K * rays));
-        if (pr->x0) NK_HIP(drx.get(pr->x0, rays * 3));
-        if (pr->segments) NK_HIP(drs.get(pr->segments, K * rays));
-        if (pr->end) NK_HIP(dre.get(pr->end, K * rays));
-    }
+    NK_TRY(call.copy_out(ctx, pm, r.casts, r.missed, r.capped));
     ctx->fc_calls = r.calls;
     if (rep) *rep = r;
     return NK_OK;
 }
 
-// k_free_map (nk_freemap.hip): the rays of nk_free_paths binned by their start cell.  Buffers of this call alone, as above; the
-// field, the mode tally and nk_free_paths' own report (fp_last) are not touched.
+// k_free_paths<*, true> (nk_freepath.hip): the rays of nk_free_paths binned by their start cell.  Buffers of this call alone, as
+// above; the field, the mode tally and nk_free_paths' own report (fp_last) are not touched.
 int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_path_grid *gr, int64_t *cells, const nk_free_path_modes *pm,
                       const nk_free_path_rays *pr, nk_free_path_map_report *rep) {
     if (rep) memset(rep, 0, sizeof(*rep));
     NK_ARG(ctx && a && gr, "nk_free_paths_map: NULL argument");
-    NK_ARG(ctx->have_material, "nk_free_paths_map: no material (nk_set_material first)");
-    NK_ARG(ctx->have_mesh, "nk_free_paths_map: no mesh (nk_set_mesh first)");
+    int64_t nlist, rays;
+    NK_TRY(nk_free_refuse(ctx, "nk_free_paths_map", a, "the lifetimes of all Q*J modes at the temperature of the estimate", nlist, rays));
     NkDev &d = ctx->d;
-    NK_ARG(a->tau, "nk_free_paths_map: tau is NULL (the lifetimes of all Q*J modes at the temperature of the estimate)");
-    NK_ARG(a->n_samples > 0, "nk_free_paths_map: n_samples = " + std::to_string(a->n_samples) + " must be positive");
-    NK_ARG(a->max_segments >= 0 && a->w_min >= 0.0, "nk_free_paths_map: max_segments and w_min must not be negative");
-    const int64_t nlist = a->modes ? (int64_t)a->n_modes : (int64_t)d.M;
-    NK_ARG(nlist >= 0, "nk_free_paths_map: n_modes must not be negative");
-    if (a->modes)
-        for (int64_t i = 0; i < nlist; ++i)
-            NK_ARG(a->modes[i] >= 0 && a->modes[i] < d.M, "nk_free_paths_map: mode " + std::to_string(a->modes[i]) + " (entry " + std::to_string((long long)i) +
-                                                              " of the list) is out of range [0, " + std::to_string(d.M) + ")");
-    for (int fc = 0; fc < d.Fc; ++fc)
-        NK_ARG(ctx->host_facets[fc].bc != 'R' || (ctx->host_facets[fc].rough >= 0 && ctx->host_facets[fc].rough < d.Fr && d.specularity),
-               "nk_free_paths_map: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
-    NK_ARG(a->x0 || d.nS > 0, "nk_free_paths_map: no start points (x0) and the mesh was set without its volume tables (simplices)");
-    const int64_t rays = nlist * (int64_t)a->n_samples;
-    NK_ARG(rays < (1ll << 31), "nk_free_paths_map: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
     // the map's own arguments
     NK_ARG(gr->weight, "nk_free_paths_map: weight is NULL (a weight vector per list entry, C_m v_m / (Q V))");
     double wmax = 0.0;
@@ -4163,32 +4126,13 @@ int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_pat
     const int64_t cap = std::max<int64_t>(rays, gr->capacity);
     r.k_K = nk_field_k(r.B_K, cap); r.k_P = nk_field_k(1.0, cap); r.k_T = nk_field_k(r.B_T, cap);
     NK_HIP(hipSetDevice(ctx->device));
-    const bool want_rays = pr && (pr->D || pr->T || pr->segments || pr->end || pr->x0);
-    NK_BUF(int32_t, dmodes, a->modes, a->modes ? nlist : 0);
-    NK_BUF(double, dtau, a->tau, d.M);
-    NK_BUF(double, dx0, a->x0, a->x0 ? rays * 3 : 0);
+    NkFreeCall call(ctx, a, pr, 1, nlist, rays);
+    NK_HIP(call.err());
     NK_BUF(double, dwt, gr->weight, nlist * 3);
-    NK_BUF(double, drows, nullptr, nlist * NK_FP_ROW);
-    NK_BUF(unsigned long long, dcnt, nullptr, nlist * NK_FP_CNT);
     NK_BUF(unsigned long long, dgrid, nullptr, (ncells + 1) * NK_FREE_MAP_LINE);
-    NK_BUF(double, drD, nullptr, (want_rays && pr->D) ? rays * 3 : 0);
-    NK_BUF(double, drT, nullptr, (want_rays && pr->T) ? rays : 0);
-    NK_BUF(double, drx, nullptr, (want_rays && pr->x0) ? rays * 3 : 0);
-    NK_BUF(int32_t, drs, nullptr, (want_rays && pr->segments) ? rays : 0);
-    NK_BUF(int32_t, dre, nullptr, (want_rays && pr->end) ? rays : 0);
     NK_BUF(int32_t, drc, nullptr, gr->ray_cell ? rays : 0);
     NK_BUF(double, drw, nullptr, gr->ray_w ? rays : 0);
-    NkFreeDev f;
-    f.modes = a->modes ? dmodes.p : nullptr;
-    f.nlist = (int32_t)nlist; f.n = a->n_samples;
-    f.max_segments = a->max_segments > 0 ? a->max_segments : 65536;
-    f.w_min = a->w_min > 0.0 ? a->w_min : ldexp(1.0, -40);
-    f.tau = dtau.p; f.vg = ctx->d_vg; f.x0 = a->x0 ? dx0.p : nullptr;
-    f.seed = a->seed ? a->seed : d.seed;
-    f.rows = drows.p; f.counts = dcnt.p;
-    f.ray_D = (want_rays && pr->D) ? drD.p : nullptr; f.ray_T = (want_rays && pr->T) ? drT.p : nullptr;
-    f.ray_x0 = (want_rays && pr->x0) ? drx.p : nullptr;
-    f.ray_seg = (want_rays && pr->segments) ? drs.p : nullptr; f.ray_end = (want_rays && pr->end) ? dre.p : nullptr;
+    const NkFreeDev f = call.dev(ctx);
     NkFreeMapDev g;
     for (int c = 0; c < 3; ++c) { g.lo[c] = gr->lo[c]; g.inv_h[c] = 1.0 / gr->h[c]; g.n[c] = gr->n[c]; }
     g.ncells = (int32_t)ncells;
@@ -4199,47 +4143,10 @@ int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_pat
     g.ray_cell = gr->ray_cell ? drc.p : nullptr; g.ray_w = gr->ray_w ? drw.p : nullptr;
     r.geometry_mode = nk_geom_mode(ctx);
     r.calls = ctx->fm_last.calls + 1;
-    r.bytes = (a->modes ? nlist * 4 : 0) + (int64_t)d.M * 8 + (a->x0 ? rays * 24 : 0) + nlist * 24 + nlist * (NK_FP_ROW + NK_FP_CNT) * 8 +
-              (ncells + 1) * NK_FREE_MAP_LINE * 8 + (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) + (f.ray_x0 ? rays * 24 : 0) +
-              (f.ray_seg ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0) + (g.ray_cell ? rays * 4 : 0) + (g.ray_w ? rays * 8 : 0);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemsetAsync(dgrid.p, 0, (size_t)(ncells + 1) * NK_FREE_MAP_LINE * 8, ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) e = nk_free_map_launch(d, f, g, r.geometry_mode, nk_lds(ctx, true), ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    NK_HIP(e);
-    r.seconds = 1e-3 * (double)ms;
-    std::vector<double> rows((size_t)nlist * NK_FP_ROW);
-    std::vector<unsigned long long> cnt((size_t)nlist * NK_FP_CNT);
-    NK_HIP(drows.get(rows.data(), nlist * NK_FP_ROW));
-    NK_HIP(dcnt.get(cnt.data(), nlist * NK_FP_CNT));
-    for (int64_t i = 0; i < nlist; ++i) {
-        const double *w = &rows[(size_t)i * NK_FP_ROW];
-        if (pm) {
-            for (int c = 0; c < 3; ++c) { if (pm->D) pm->D[3 * i + c] = w[c]; if (pm->D2) pm->D2[3 * i + c] = w[3 + c]; }
-            if (pm->T) pm->T[i] = w[6];
-            if (pm->hits) pm->hits[i] = w[7];
-            if (pm->p_res) pm->p_res[i] = w[8];
-            if (pm->p_wall) pm->p_wall[i] = w[9];
-            if (pm->w_left) pm->w_left[i] = w[10];
-            if (pm->p_int) pm->p_int[i] = w[11];
-        }
-        r.casts += (int64_t)cnt[(size_t)i * NK_FP_CNT]; r.missed += (int64_t)cnt[(size_t)i * NK_FP_CNT + 1]; r.capped += (int64_t)cnt[(size_t)i * NK_FP_CNT + 2];
-    }
-    if (want_rays) {
-        if (pr->D) NK_HIP(drD.get(pr->D, rays * 3));
-        if (pr->T) NK_HIP(drT.get(pr->T, rays));
-        if (pr->x0) NK_HIP(drx.get(pr->x0, rays * 3));
-        if (pr->segments) NK_HIP(drs.get(pr->segments, rays));
-        if (pr->end) NK_HIP(dre.get(pr->end, rays));
-    }
+    r.bytes = call.bytes() + nlist * 24 + (ncells + 1) * NK_FREE_MAP_LINE * 8 + (g.ray_cell ? rays * 4 : 0) + (g.ray_w ? rays * 8 : 0);
+    NK_HIP(hipMemsetAsync(dgrid.p, 0, (size_t)(ncells + 1) * NK_FREE_MAP_LINE * 8, ctx->stream));      // (outside the timed window)
+    NK_HIP(nk_free_timed(ctx->stream, r.seconds, [&] { return nk_free_paths_launch(d, f, &g, r.geometry_mode, nk_lds(ctx, true), ctx->stream); }));
+    NK_TRY(call.copy_out(ctx, pm, &r.casts, &r.missed, &r.capped));
     if (gr->ray_cell) NK_HIP(drc.get(gr->ray_cell, rays));
     if (gr->ray_w) NK_HIP(drw.get(gr->ray_w, rays));
     NK_HIP(hipMemcpy(cells, dgrid.p, (size_t)ncells * NK_FREE_MAP_LINE * 8, hipMemcpyDeviceToHost));

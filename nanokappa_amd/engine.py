@@ -740,6 +740,52 @@ class Engine(object):
         return dict(rays=int(r.rays), casts=int(r.casts), missed=int(r.missed), capped=int(r.capped),
                     geometry_mode=int(r.geometry_mode), calls=int(r.calls), bytes=int(r.bytes), seconds=float(r.seconds))
 
+    def _free_path_call(self, who, tau, n, modes, max_segments, w_min, x0, seed, rays, columns=False):
+        """What free_paths, free_path_columns and free_path_map hand to the library.  tau [Q*J], or [K, Q*J] with `columns`;
+        modes None = every mode with |v| > 0 and tau > 0 (in at least one column).  `who` opens the messages.  Returns
+        (args, modes struct, rays struct or None, out, list or None): out holds the zeroed result arrays the structs point to,
+        with a leading K axis for the columns."""
+        if columns:
+            t = None if tau is None else _d(tau)
+            if t is not None and (t.ndim != 2 or (self.M > 0 and t.shape[1] != self.M)):
+                raise NkError('%s: taus must be [K, %d] (a row of lifetimes per column), got shape %s' % (who, self.M, t.shape))
+            lead = (0 if t is None else min(int(t.shape[0]), FREE_PATH_MAX_COLUMNS),)                 # (a refused call writes nothing)
+        else:
+            t = None if tau is None else _d(np.ravel(tau))
+            if t is not None and self.M > 0 and t.shape[0] != self.M:
+                raise NkError('%s: tau has %d entries, the material %d modes' % (who, t.shape[0], self.M))
+            lead = ()
+        if modes is None and t is not None and self.M > 0 and t.shape[0] > 0:
+            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & ((t > 0).any(axis=0) if columns else t > 0))[0]
+        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
+        L = self.M if ml is None else int(ml.shape[0])
+        nn = max(n, 0)
+        xs = None
+        if x0 is not None:
+            xs = _d(x0)
+            if xs.size != L * nn * 3:
+                raise NkError('%s: x0 needs %d x %d x 3 entries, got %d' % (who, L, n, xs.size))
+        a = nk_free_path_args()
+        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
+        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
+        a._keep = (t, xs, ml)                                # (the arrays the pointers refer to)
+        rows = lead + (L,)
+        out = dict(D=np.zeros(rows + (3,)), D2=np.zeros(rows + (3,)), T=np.zeros(rows), hits=np.zeros(rows), p_res=np.zeros(rows),
+                   p_wall=np.zeros(rows), w_left=np.zeros(rows), p_int=np.zeros(rows))
+        pm = nk_free_path_modes()
+        for k in out:
+            setattr(pm, k, _p(out[k]))
+        pr = None
+        if rays:
+            per = rows + (nn,)
+            ro = dict(ray_D=np.zeros(per + (3,)), ray_T=np.zeros(per), ray_segments=np.zeros(per, dtype=np.int32),
+                      ray_end=np.zeros(per, dtype=np.int32), ray_x0=np.zeros((L, nn, 3)))
+            pr = nk_free_path_rays()
+            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
+            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
+            out.update(ro)
+        return a, pm, pr, out, ml
+
     def free_paths(self, tau, n=64, modes=None, max_segments=0, w_min=0.0, x0=None, seed=0, rays=False):
         """Free-path sampling (nk_free_paths; k_free_paths): n rays for every mode of `modes` (global indices q*J + j; None =
         every mode with |v| > 0 and tau > 0; 'all' = all Q*J modes), flown along the mode's group velocity until a boundary or the lifetime tau [Q*J] ends them.  x0
@@ -748,37 +794,10 @@ class Engine(object):
         p_wall, w_left, p_int [L], and report (rays, casts, missed, capped, geometry_mode, calls, bytes, seconds); with
         rays=True also ray_D [L, n, 3], ray_T, ray_segments, ray_end, ray_x0 (end codes: 0 weight exhausted, 1 reservoir,
         2 diffuse wall, 3 miss, 4 cap).  Touches neither the particles nor the step counter."""
-        a = nk_free_path_args()
-        t = None if tau is None else _d(np.ravel(tau))
-        if t is not None and self.M > 0 and t.shape[0] != self.M:
-            raise NkError('free_paths: tau has %d entries, the material %d modes' % (t.shape[0], self.M))
-        if modes is None and t is not None and self.M > 0:
-            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & (t > 0))[0]
-        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
-        L = self.M if ml is None else int(ml.shape[0])
         n = int(n)
-        xs = None
-        if x0 is not None:
-            xs = _d(x0)
-            if xs.size != L * max(n, 0) * 3:
-                raise NkError('free_paths: x0 needs %d x %d x 3 entries, got %d' % (L, n, xs.size))
-        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
-        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
-        R = L * max(n, 0)
-        out = dict(D=np.zeros((L, 3)), D2=np.zeros((L, 3)), T=np.zeros(L), hits=np.zeros(L), p_res=np.zeros(L), p_wall=np.zeros(L),
-                   w_left=np.zeros(L), p_int=np.zeros(L))
-        pm = nk_free_path_modes()
-        for k in out:
-            setattr(pm, k, _p(out[k]))
-        pr = nk_free_path_rays()
-        if rays:
-            ro = dict(ray_D=np.zeros((L, n, 3)), ray_T=np.zeros((L, n)), ray_segments=np.zeros((L, n), dtype=np.int32),
-                      ray_end=np.zeros((L, n), dtype=np.int32), ray_x0=np.zeros((L, n, 3)))
-            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
-            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
-            out.update(ro)
+        a, pm, pr, out, ml = self._free_path_call('free_paths', tau, n, modes, max_segments, w_min, x0, seed, rays)
         rep = nk_free_path_report()
-        self._ck(self.L.nk_free_paths(self.h, C.byref(a), C.byref(pm), C.byref(pr) if rays else None, C.byref(rep)), 'nk_free_paths')
+        self._ck(self.L.nk_free_paths(self.h, C.byref(a), C.byref(pm), C.byref(pr) if pr else None, C.byref(rep)), 'nk_free_paths')
         out.update(modes=(np.arange(self.M, dtype=np.int32) if ml is None else ml.copy()), n=n, report=self._free_path_report(rep))
         return out
 
@@ -797,41 +816,11 @@ class Engine(object):
         actually made --, n_columns, tile -- the columns that share a cast; more are flown in tiles that repeat the casts --,
         launches, geometry_mode, calls, bytes, seconds); with rays=True also ray_D [K, L, n, 3], ray_T, ray_segments, ray_end
         [K, L, n] and ray_x0 [L, n, 3].  free_sweep.column(res, c) gives column c in the shape of a free_paths result."""
-        a = nk_free_path_args()
-        t = None
-        if taus is not None:
-            t = _d(taus)
-            if t.ndim != 2 or (self.M > 0 and t.shape[1] != self.M):
-                raise NkError('free_path_columns failed (%d): taus must be [K, %d] (a row of lifetimes per column), got shape %s' % (ERR_ARG, self.M, t.shape))
-        K = 0 if t is None else int(t.shape[0])
-        if modes is None and t is not None and self.M > 0 and K > 0:
-            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & (t > 0).any(axis=0))[0]
-        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
-        L = self.M if ml is None else int(ml.shape[0])
         n = int(n)
-        xs = None
-        if x0 is not None:
-            xs = _d(x0)
-            if xs.size != L * max(n, 0) * 3:
-                raise NkError('free_path_columns failed (%d): x0 needs %d x %d x 3 entries, got %d' % (ERR_ARG, L, n, xs.size))
-        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
-        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
-        Ka = max(min(K, FREE_PATH_MAX_COLUMNS), 0)           # (a refused call writes nothing)
-        out = dict(D=np.zeros((Ka, L, 3)), D2=np.zeros((Ka, L, 3)), T=np.zeros((Ka, L)), hits=np.zeros((Ka, L)), p_res=np.zeros((Ka, L)),
-                   p_wall=np.zeros((Ka, L)), w_left=np.zeros((Ka, L)), p_int=np.zeros((Ka, L)))
-        pm = nk_free_path_modes()
-        for k in out:
-            setattr(pm, k, _p(out[k]))
-        pr = nk_free_path_rays()
-        if rays:
-            nn = max(n, 0)
-            ro = dict(ray_D=np.zeros((Ka, L, nn, 3)), ray_T=np.zeros((Ka, L, nn)), ray_segments=np.zeros((Ka, L, nn), dtype=np.int32),
-                      ray_end=np.zeros((Ka, L, nn), dtype=np.int32), ray_x0=np.zeros((L, nn, 3)))
-            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
-            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
-            out.update(ro)
+        a, pm, pr, out, ml = self._free_path_call('free_path_columns failed (%d)' % ERR_ARG, taus, n, modes, max_segments, w_min, x0, seed, rays, columns=True)
+        K = 0 if taus is None else int(np.shape(taus)[0])
         rep = nk_free_path_columns_report()
-        self._ck(self.L.nk_free_paths_columns(self.h, C.byref(a), K if t is not None else 1, C.byref(pm), C.byref(pr) if rays else None, C.byref(rep)),
+        self._ck(self.L.nk_free_paths_columns(self.h, C.byref(a), K if taus is not None else 1, C.byref(pm), C.byref(pr) if pr else None, C.byref(rep)),
                  'nk_free_paths_columns')
         out.update(modes=(np.arange(self.M, dtype=np.int32) if ml is None else ml.copy()), n=n, columns=K,
                    casts=np.array(rep.casts[:K], dtype=np.int64), missed=np.array(rep.missed[:K], dtype=np.int64),
@@ -849,7 +838,7 @@ class Engine(object):
 
     def free_path_map(self, tau, weight, lo, h, n_cells, n=64, modes=None, max_segments=0, w_min=0.0, x0=None, seed=0, rays=True,
                       capacity=0, weight_bound=0.0):
-        """Free-path map (nk_free_paths_map; k_free_map): the rays of free_paths(tau, n, modes, ...) binned on the device by the
+        """Free-path map (nk_free_paths_map; k_free_paths with its map statements): the rays of free_paths(tau, n, modes, ...) binned on the device by the
         cell of their START point on the grid (lo, h, n_cells) -- the field's convention.  weight [L, 3]: per list entry the
         vector w whose products w_a D_b are summed (free_map.weights: C_m v_m / (Q V)); capacity / weight_bound: floors under the
         ray count and under max |weight| when the scales are derived (pin them to add the cells of several calls).  Returns the
@@ -858,27 +847,14 @@ class Engine(object):
         with rays=True also the per-ray outputs of free_paths and ray_cell [L, n] (flat cell index), ray_w [L, n] (the final weight
         that went to p_res, p_wall or w_left; 0 otherwise).  Touches neither the particles, the step counter, the field nor
         free_paths_info()."""
-        a = nk_free_path_args()
-        t = None if tau is None else _d(np.ravel(tau))
-        if t is not None and self.M > 0 and t.shape[0] != self.M:
-            raise NkError('free_path_map: tau has %d entries, the material %d modes' % (t.shape[0], self.M))
-        if modes is None and t is not None and self.M > 0:
-            modes = np.nonzero((np.abs(self._vg).max(axis=1) > 0) & (t > 0))[0]
-        ml = None if (modes is None or isinstance(modes, str)) else _i(np.ravel(modes))
-        L = self.M if ml is None else int(ml.shape[0])
         n = int(n)
-        xs = None
-        if x0 is not None:
-            xs = _d(x0)
-            if xs.size != L * max(n, 0) * 3:
-                raise NkError('free_path_map: x0 needs %d x %d x 3 entries, got %d' % (L, n, xs.size))
+        a, pm, pr, out, ml = self._free_path_call('free_path_map', tau, n, modes, max_segments, w_min, x0, seed, rays)
+        L = a.n_modes
         w = None
         if weight is not None:
             w = _d(weight)
             if w.size != L * 3:
                 raise NkError('free_path_map: weight needs %d x 3 entries (a vector per list entry), got %d' % (L, w.size))
-        a.n_modes, a.modes, a.n_samples, a.max_segments = L, _p(ml, c_ip), n, int(max_segments)
-        a.w_min, a.tau, a.x0, a.seed = float(w_min), _p(t), _p(xs), int(seed)
         nc = [int(k) for k in np.ravel(n_cells)]
         g = nk_free_path_grid()
         g.n[:] = nc
@@ -887,24 +863,13 @@ class Engine(object):
         g.weight, g.capacity, g.weight_bound = _p(w), int(capacity), float(weight_bound)
         ok = min(nc) > 0 and nc[0] * nc[1] * nc[2] <= (1 << 24)         # (a refused call writes nothing)
         cells = np.zeros(tuple(nc) + (FREE_MAP_LINE,) if ok else (1,), dtype=np.int64)
-        nn = max(n, 0)
-        out = dict(D=np.zeros((L, 3)), D2=np.zeros((L, 3)), T=np.zeros(L), hits=np.zeros(L), p_res=np.zeros(L), p_wall=np.zeros(L),
-                   w_left=np.zeros(L), p_int=np.zeros(L))
-        pm = nk_free_path_modes()
-        for k in out:
-            setattr(pm, k, _p(out[k]))
-        pr = nk_free_path_rays()
         if rays:
-            ro = dict(ray_D=np.zeros((L, nn, 3)), ray_T=np.zeros((L, nn)), ray_segments=np.zeros((L, nn), dtype=np.int32),
-                      ray_end=np.zeros((L, nn), dtype=np.int32), ray_x0=np.zeros((L, nn, 3)), ray_cell=np.zeros((L, nn), dtype=np.int32),
-                      ray_w=np.zeros((L, nn)))
-            pr.D, pr.T, pr.x0 = _p(ro['ray_D']), _p(ro['ray_T']), _p(ro['ray_x0'])
-            pr.segments, pr.end = _p(ro['ray_segments'], c_ip), _p(ro['ray_end'], c_ip)
+            ro = dict(ray_cell=np.zeros((L, max(n, 0)), dtype=np.int32), ray_w=np.zeros((L, max(n, 0))))
             g.ray_cell, g.ray_w = _p(ro['ray_cell'], c_ip), _p(ro['ray_w'])
             out.update(ro)
         rep = nk_free_path_map_report()
         self._ck(self.L.nk_free_paths_map(self.h, C.byref(a), C.byref(g), cells.ctypes.data_as(C.POINTER(C.c_int64)) if ok else None,
-                                          C.byref(pm), C.byref(pr) if rays else None, C.byref(rep)), 'nk_free_paths_map')
+                                          C.byref(pm), C.byref(pr) if pr else None, C.byref(rep)), 'nk_free_paths_map')
         out.update(modes=(np.arange(self.M, dtype=np.int32) if ml is None else ml.copy()), n=n, cells=cells,
                    report=self._free_path_map_report(rep))
         return out

@@ -1,5 +1,5 @@
-"""Cost of a free-path map (k_free_map, nk_free_paths_map): device time of a map call on 16^3, 64^3 and 128^3 grids against the
-plain call (k_free_paths, nk_free_paths) with the same arguments in the same process.  BASELINE config 2's material and box
+"""Cost of a free-path map (k_free_paths<GEOM, true>, nk_free_paths_map): device time of a map call on 16^3, 64^3 and 128^3 grids against the
+plain call (k_free_paths<GEOM, false>, nk_free_paths) with the same arguments in the same process.  BASELINE config 2's material and box
 (178 740 modes in the list, n = 64; planes in LDS) and the 72-sided wire of the tests (golden material, every active mode, n = 64;
 the face tree).  The legs alternate; five repeats after one warm-up call each; medians and ranges (`seconds` of the calls'
 reports: HIP events around the launch; the map's excludes the clearing of its grid).

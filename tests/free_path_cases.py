@@ -12,7 +12,7 @@ from util import case_tables, case_from_args
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'oracle'))
 import nk_oracle as O  # noqa: E402
 
-TAG_FREE = 0x50000            # NK_TAG_FREE (nanokappa_amd/csrc/nk_freepath.h)
+TAG_FREE = 0x50000            # NK_TAG_FREE (nanokappa_amd/csrc/nk_freepath.h; the draws are made in nk_flight.h)
 W_MIN = 2.0 ** -40
 MAX_SEGMENTS = 65536
 _CACHE = {}
@@ -322,3 +322,100 @@ def parity_run(name, fused=True):
     p = PARITY[name]
     ct = case(p['case'])
     return run_case(p['case'], p['modes'](ct), p['n'], p['seed'], max_segments=p['max_segments'], fused=fused)
+
+
+# ------------------------------------------------------------------------------------------- recorded results
+# The three free-path calls on short lists that reach every branch of the flight (tests/test_gpu_free_flight.py holds the engine
+# against tests/golden/free_flight_<name>.npz, which scripts/free_path_golden.py records): name -> case, active modes in the list,
+# rays per mode, max_segments, seed.  Every list also holds a mode that takes no cast and its first mode a second time.
+GOLDEN = {
+    'ttp': dict(case='ttp', active=4, n=100, max_segments=8, seed=31),          # periodic walls; the rays end by the cap
+    'ttrrp_k': dict(case='ttrrp_k', active=4, n=64, max_segments=0, seed=32),   # specular turns, degenerate partner, diffuse ends
+    'wire72': dict(case='wire72', active=3, n=64, max_segments=0, seed=33),     # the face tree; five entries: a workgroup of one wave
+}
+GOLDEN_COLUMNS = np.array([0.25, 0.375, 0.5, 0.75, 1.0, 1.5, 2.0, 3.0, 4.0])    # nine: one more than the column tile
+GOLDEN_GRID = (3, 2, 2)
+
+
+def golden_inputs(name):
+    """What the recorded calls of a case are made with: tau [M], modes [L], weight [L, 3], the grid (lo, h, n_cells) -- lo is moved
+    into the solid by 0.3 cells, so some start points lie outside the grid and are clamped -- and, for 'ttrrp_k', a table of
+    degenerate partners (the case's own names none for a mode that a reflection leads to)."""
+    from nanokappa_amd import field as FD
+    from test_free_map_host import case_weights
+    p = GOLDEN[name]
+    ct = case(p['case'])
+    tau = np.array(lifetimes(ct), dtype=np.float64)
+    v = group_vel(ct)
+    act = spread_modes(ct, p['active'])
+    b = np.asarray(ct['mesh']['bounds'], dtype=np.float64).reshape(2, 3)
+    out = {}
+    if name == 'ttp':
+        # two modes that fly along the reservoirs and meet periodic walls alone: one ends by the cap, the other, with a lifetime of
+        # a tenth of a crossing, by its weight
+        along = active_modes(ct)
+        along = along[v[along, 0] == 0]
+        act = np.array([along[0], act[1], along[along.shape[0] // 2], act[2]])
+        tau[act[2]] = (b[1] - b[0]).max() / (10.0 * np.abs(v[act[2]]).max())
+    if name == 'ttrrp_k':
+        # modes that a rough facet reflects specularly, as often as the tables allow, into another mode; every second mode gets
+        # the next branch at its wave vector as its degenerate partner
+        r, J = ct['rough'], ct['J']
+        sp = np.where(np.asarray(r['true_spec']) & (np.asarray(r['spec_map']) >= 0), np.asarray(r['specularity']), 0.0).max(axis=0)
+        cand = np.intersect1d(np.nonzero(sp >= 0.9 * sp.max())[0], active_modes(ct))
+        act = cand[np.linspace(0, cand.shape[0] - 1, p['active']).astype(int)]
+        m = np.arange(v.shape[0])
+        out['degen_j2'] = np.where(m % 2 == 0, (m % J + 1) % J, -1).astype(np.int32)
+    idle = np.nonzero(~((np.abs(v).max(axis=1) > 0) & (tau > 0)))[0]
+    modes = np.concatenate([act[:2], idle[:1], act[2:], act[:1]]).astype(np.int32)
+    lo, h, n = FD.grid_from_bounds(b, GOLDEN_GRID)
+    lo = np.asarray(lo, dtype=np.float64) + 0.3 * np.asarray(h, dtype=np.float64)
+    out.update(tau=tau, modes=modes, weight=case_weights(ct, modes)[1], lo=lo, h=np.asarray(h, dtype=np.float64), n_cells=np.asarray(n, dtype=np.int32))
+    return out
+
+
+def golden_case(name, inp):
+    """The case's tables as the recorded calls use them (inp: golden_inputs, or the same read from the fixture)."""
+    ct = case(GOLDEN[name]['case'])
+    if 'degen_j2' in inp:
+        ct = dict(ct, rough=dict(ct['rough'], degen_j2=np.asarray(inp['degen_j2'], dtype=np.int32)))
+    return ct
+
+
+MODE_KEYS = ('D', 'D2', 'T', 'hits', 'p_res', 'p_wall', 'w_left', 'p_int')
+RAY_KEYS = ('ray_D', 'ray_T', 'ray_segments', 'ray_end', 'ray_x0')
+
+
+def golden_calls(eng, name, inp):
+    """The recorded calls on an engine with the case's tables, with n rays per mode and with one.  Returns (out, same): out, a flat
+    dict of the arrays that are recorded -- <n>_x0 (drawn by the seed), <n>_paths_*, <n>_map_*, <n>_cols_* with <n> = 'n' or 'one'
+    --, and same, {name: (array, key of out)}: the outputs that repeat a recorded array and are held against that one instead."""
+    p = GOLDEN[name]
+    tau, modes, kw = inp['tau'], inp['modes'], dict(max_segments=p['max_segments'], seed=p['seed'])
+    out, same = {}, {}
+    for tag, n in (('n', p['n']), ('one', 1)):
+        x0 = eng.free_paths(tau, n=n, modes=modes, rays=True, **kw)['ray_x0']
+        out[tag + '_x0'] = x0
+        r = eng.free_paths(tau, n=n, modes=modes, x0=x0, rays=True, **kw)
+        for k in MODE_KEYS + RAY_KEYS[:-1]:
+            out['%s_paths_%s' % (tag, k)] = r[k]
+        same[tag + '_paths_ray_x0'] = (r['ray_x0'], tag + '_x0')
+        out[tag + '_paths_counts'] = np.array([r['report'][k] for k in ('rays', 'casts', 'missed', 'capped')], dtype=np.int64)
+        r = eng.free_path_map(tau, inp['weight'], inp['lo'], inp['h'], inp['n_cells'], n=n, modes=modes, x0=x0, rays=True, **kw)
+        for k in ('cells', 'ray_cell', 'ray_w'):
+            out['%s_map_%s' % (tag, k)] = r[k]
+        for k in MODE_KEYS + RAY_KEYS[:-1]:
+            same['%s_map_%s' % (tag, k)] = (r[k], '%s_paths_%s' % (tag, k))
+        same[tag + '_map_ray_x0'] = (r['ray_x0'], tag + '_x0')
+        rep = r['report']
+        out[tag + '_map_counts'] = np.array([rep[k] for k in ('rays', 'casts', 'missed', 'capped', 'clamped', 'overflow', 'k_K', 'k_P', 'k_T')], dtype=np.int64)
+        out[tag + '_map_bounds'] = np.array([rep['B_K'], rep['B_T']])
+        r = eng.free_path_columns(tau[None, :] * GOLDEN_COLUMNS[:, None], n=n, modes=modes, x0=x0, rays=True, **kw)
+        for k in MODE_KEYS + ('casts', 'missed', 'capped'):
+            out['%s_cols_%s' % (tag, k)] = r[k]
+        out[tag + '_cols_shared'] = np.array([r['report']['casts_shared']], dtype=np.int64)
+        for k in RAY_KEYS[:-1]:                             # column 4 has the factor 1: the plain call's rays
+            same['%s_cols_%s_4' % (tag, k)] = (r[k][4], '%s_paths_%s' % (tag, k))
+        same[tag + '_cols_ray_x0'] = (r['ray_x0'], tag + '_x0')
+        out[tag + '_cols_ends'] = np.stack([np.bincount(e.ravel(), minlength=5) for e in r['ray_end']]).astype(np.int64)
+    return out, same

@@ -1,4 +1,4 @@
-"""Free-path maps on the GPU (Engine.free_path_map; k_free_map): the rows and rays are nk_free_paths' own bit for bit; the cells
+"""Free-path maps on the GPU (Engine.free_path_map; k_free_paths<GEOM, true>): the rows and rays are nk_free_paths' own bit for bit; the cells
 are free_map.tally of the call's own per-ray outputs bit for bit; clamping; order and list independence; the sum identity; the
 closed form per slab cell; non-interference; the refusals; Population.free_path_map and --free_path_map.
 
