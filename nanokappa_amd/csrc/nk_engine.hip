@@ -1431,7 +1431,12 @@ static int nk_build_mode_map(nk_ctx *ctx) {
     return NK_OK;
 }
 
-// Upper bound of the particles that can enter one segment in one step (the sweep's halt criterion uses the same sum).
+// Particles that can enter one segment in one step, as the host sizes the store: the fullest segment's sum of floor(p) + 1 over its
+// (reservoir, mode) entries, divided by the rank count ONCE (rounded up), plus R.  The sweep's halt criterion does not use this
+// figure but the sum nk_emit_one leaves in seg_bound, which rounds up entry by entry -- a rank can own ceil(c / nranks) of an entry's
+// c levels -- and so exceeds this one by less than one per entry, R (nl - 1) in all, from two ranks on.  That lowers the live count
+// at which a segment asks for room by as much; a freshly uploaded store has a third of a segment and 107 slots more than that to
+// spare (DESIGN.md (e) has the arithmetic, tests/test_shards_host.py the two sums, tests/test_gpu_shards.py the measurement).
 static int64_t nk_spawn_bound(const nk_ctx *ctx, int nseg) {
     const NkDev &d = ctx->d;
     if (d.R <= 0) return 0;

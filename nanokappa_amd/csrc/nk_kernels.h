@@ -491,7 +491,9 @@ __device__ __forceinline__ int nk_emit_one(const NkDev &d, const NkLds &L, uint3
                 idx = d.part ? (int)(cw >> 18) : (int)((uint32_t)rm - (uint32_t)r * (uint32_t)d.M);
                 cval = sp_cv[lo];
                 prob = sp_pr[lo];
-                // the q-th level this rank owns, counted down from c (nk_emit_entry's order)
+                // the q-th level this rank owns, counted down from c (nk_emit_entry's order).  Any n: the rank owns the levels with
+                // (rm + level + step) % n == rank, i.e. level = tq (mod n); (c - tq) mod n is how far c lies above the nearest of
+                // them, so top = c - (c + n - tq) % n is the largest level <= c congruent to tq, and the q-th is n q below it
                 if (d.nranks == 1) level = c - q;
                 else {
                     const uint32_t n = (uint32_t)d.nranks;

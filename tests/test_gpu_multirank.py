@@ -2,7 +2,8 @@
 vector is all-reduced in the engine's stream.  The union of the two shards must equal the single-rank run particle for
 particle (ids, modes, positions), and both ranks must report the same, whole-ensemble tallies.  Skipped where fewer than
 two GPUs are visible (the one-GPU development box); the same scheme runs on CPU in test_sharding_gloo.py and, without a
-communicator, on one GPU in test_gpu_parity.py::test_two_rank_sharding_on_one_gpu."""
+communicator, on one GPU in test_gpu_parity.py::test_two_rank_sharding_on_one_gpu (two ranks) and in test_gpu_shards.py (3, 5
+and 8 ranks, up to ten particles per entry, all three generators)."""
 import multiprocessing as mp
 import os
 import sys

@@ -1,6 +1,8 @@
 """The N > 1 path on CPU: two processes (torch.distributed, gloo) each advance their shard of the ensemble with the
 oracle, summing the per-step tally vector with an all-reduce -- the scheme the HIP engine runs over RCCL.  The union
-of the two shards must reproduce the single-process run particle for particle."""
+of the two shards must reproduce the single-process run particle for particle.  The oracle's shards at 3, 5 and 8 ranks with
+up to ten particles per entry (no process group: an all-reduce that sums nothing): test_shards_host.py; engine contexts against
+them on one GPU: test_gpu_shards.py."""
 import os
 import sys
 
