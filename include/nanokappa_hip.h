@@ -584,6 +584,32 @@ const char *nk_group_last_error(const nk_group *g);   /* g may be NULL: error of
 /* device versions of the reference's primitives, for parity tests (tests/ -m gpu) */
 int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
                      double *xc, double *tc, int32_t *fc);                       /* Mesh.py:806-856 */
+/* The same cast for rays that start on a named facet, as an entering particle starts on its reservoir: per ray the facet skip
+ * is formed as the sweep forms it (nk_tree_skip: the facet's centroid and normal, the ray) and handed to the walk of the face
+ * tree.  from_facet[i] = -1 or any value outside [0, facets): no skip.  skipped[i] = 1 where the walk left out the nodes that
+ * hold only faces of from_facet[i]; 0 everywhere on a mesh of at most 256 faces and facets (no tree).  (xc, tc, fc) as above:
+ * the skip never changes a result. */
+int nk_find_boundary_from(nk_ctx *ctx, int64_t n, const double *x /* [n*3] */, const double *v /* [n*3] */,
+                          const int32_t *from_facet /* [n] */, double *xc, double *tc, int32_t *fc, int32_t *skipped /* [n] */);
+/* A read-only view of the face tree that nk_set_mesh built (meshes of more than 256 faces or facets; NG = 0 and all else 0
+ * without one).  Level 0 holds one box per leaf (the union of the boxes of its four slots), level l + 1 one box per four nodes of
+ * level l, up to tree_top, whose nodes are the top family. */
+typedef struct {
+    int32_t NG;                  /* 1: the casts walk the tree, 0: they sweep all planes */
+    int32_t tree_top;            /* index of the top level */
+    int32_t level_nodes[8];      /* nodes per level (without the padding nodes that fill a level up to a multiple of 4) */
+    int32_t tree_base[8];        /* first box of each level in family_boxes, in boxes of 6 floats */
+    int32_t top_family;          /* nodes of the top level: 2..4 (1 for a tree of a single leaf) */
+    int32_t tree_leaves;         /* leaf records, 4 slots each */
+    int32_t references;          /* face references in the leaves (a sliver is referred to several times) */
+    int32_t pad_slots;           /* leaf slots without a face */
+    int32_t n_families;          /* families of four boxes over all levels */
+    int32_t pad_;
+    double tree_bound;           /* largest |coordinate| of a box */
+} nk_tree_report;
+/* family_boxes [n_families * 24] floats (per family four boxes lo(3) hi(3); padding boxes have lo > hi), leaf_boxes
+ * [tree_leaves * 24] floats (the boxes of a leaf's four slots); either may be NULL.  Call once with NULLs for the sizes. */
+int nk_tree_info(nk_ctx *ctx, nk_tree_report *out, float *family_boxes, float *leaf_boxes);
 int nk_classify(nk_ctx *ctx, int64_t n, const double *x, int32_t *id);           /* Geometry.py:1212 */
 /* The box store's wall functions (nk_device.h) on n rays, with the context's walls, tol and dt; NK_ERR_ARG unless nk_set_mesh
  * found a box.  which: 0 nk_box_out (t = 1.0 / 0.0, facet = -1; x is the end-of-step position), 1 nk_box_first_hit (t = the

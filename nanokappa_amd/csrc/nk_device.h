@@ -792,12 +792,19 @@ struct NkRayF { float ix, iy, iz, nx, ny, nz, fx, fy, fz; };
 // more than the rounding margin c, and the widening e = c |1 / v| = c 1e30 makes every position in between pass -- the same
 // answers as an explicit "parallel and outside?" test, with no special case.  |lo - x| < 1e5 keeps every product finite.
 // Conservative like before: a box that is entered although the exact ray misses it costs time, never a hit.
+// DOMAIN: the largest |v_a| of a ray is at least 1e-20.  A component below 1e-30 in magnitude is clamped to +-NK_RAY_BIG and so
+// treated as parallel; that is right as long as the ray moves along that axis, over its whole flight, by less than the margin
+// c = (|x| + B) 2^-20: with the largest component >= 1e-20 the ratio of the two is below 1e-10 and the drift over a flight of at
+// most 4 (|x| + B) below 4e-10 (|x| + B).  A ray whose EVERY component lies below 1e-30 (v = (1e-36, 3e-36, 0), say) has all
+// its 1 / v clamped to the same value: the slab test then follows the direction (+-1, +-1, +-1) instead of the ray's and the walk
+// misses hits that the plane sweep finds (measured: 20 of 20 such rays on a 288-face wire, profiles/tree_edge_margins.txt).  Group
+// velocities are of order 1 .. 1e2 A/ps, and a mode with v = 0 exactly is parallel to every axis and correctly never hits.
 #define NK_RAY_BIG 1.0e30f
 __device__ __forceinline__ NkRayF nk_ray_f32(double x, double y, double z, double vx, double vy, double vz, double B) {
     NkRayF r;
     const float fx = (float)x, fy = (float)y, fz = (float)z;
     r.ix = vx != 0.0 ? (float)(1.0 / vx) : NK_RAY_BIG; r.iy = vy != 0.0 ? (float)(1.0 / vy) : NK_RAY_BIG; r.iz = vz != 0.0 ? (float)(1.0 / vz) : NK_RAY_BIG;
-    // (a component so small that 1 / v overflows a float is as good as parallel)
+    // (a component so small that 1 / v exceeds NK_RAY_BIG is as good as parallel -- next to a component of at least 1e-20: DOMAIN above)
     r.ix = fminf(fmaxf(r.ix, -NK_RAY_BIG), NK_RAY_BIG); r.iy = fminf(fmaxf(r.iy, -NK_RAY_BIG), NK_RAY_BIG); r.iz = fminf(fmaxf(r.iz, -NK_RAY_BIG), NK_RAY_BIG);
     const float k = 9.5367431640625e-07f;                                               // 2^-20
     const float ex = (fabsf(fx) + (float)B) * k * fabsf(r.ix), ey = (fabsf(fy) + (float)B) * k * fabsf(r.iy), ez = (fabsf(fz) + (float)B) * k * fabsf(r.iz);

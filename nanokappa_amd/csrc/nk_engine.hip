@@ -3526,6 +3526,53 @@ int nk_find_boundary(nk_ctx *ctx, int64_t n, const double *x, const double *v, d
     NK_HIP(dxc.get(xc, n * 3)); NK_HIP(dtc.get(tc, n)); NK_HIP(dfc.get(fc, n));
     return NK_OK;
 }
+int nk_find_boundary_from(nk_ctx *ctx, int64_t n, const double *x, const double *v, const int32_t *from_facet, double *xc, double *tc,
+                          int32_t *fc, int32_t *skipped) {
+    NK_ARG(ctx && ctx->have_mesh && ctx->have_sv && n > 0 && x && v && from_facet, "nk_find_boundary_from: bad arguments");
+    NK_HIP(hipSetDevice(ctx->device));
+    NkDev &d = ctx->d;
+    NK_BUF(double, dx, x, n * 3); NK_BUF(double, dv, v, n * 3); NK_BUF(int32_t, dff, from_facet, n);
+    NK_BUF(double, dxc, nullptr, n * 3); NK_BUF(double, dtc, nullptr, n); NK_BUF(int32_t, dfc, nullptr, n); NK_BUF(int32_t, dsk, nullptr, n);
+    NK_GEOM_LAUNCH(k_tap_find_boundary_from, (int)((n + NK_WG - 1) / NK_WG), nk_lds(ctx, true), d, n, dx.p, dv.p, dff.p, dxc.p, dtc.p, dfc.p, dsk.p);
+    NK_HIP(hipGetLastError());
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    NK_HIP(dxc.get(xc, n * 3)); NK_HIP(dtc.get(tc, n)); NK_HIP(dfc.get(fc, n)); NK_HIP(dsk.get(skipped, n));
+    return NK_OK;
+}
+// The face tree as nk_set_mesh left it on the device, read back: nothing is kept on the host but NkDev's few numbers, so the counts
+// are taken from the leaf records themselves (a padding slot is a face box no ray enters, lo > hi).
+int nk_tree_info(nk_ctx *ctx, nk_tree_report *out, float *family_boxes, float *leaf_boxes) {
+    NK_ARG(ctx && out && ctx->have_mesh, "nk_tree_info: no mesh");
+    memset(out, 0, sizeof(*out));
+    const NkDev &d = ctx->d;
+    out->NG = d.NG;
+    if (d.NG == 0) return NK_OK;
+    NK_HIP(hipSetDevice(ctx->device));
+    out->tree_top = d.tree_top;
+    out->tree_leaves = d.tree_leaves;
+    out->tree_bound = d.tree_bound;
+    out->n_families = d.tree_nfam;
+    int count = d.tree_leaves;
+    for (int l = 0; l <= d.tree_top && l < NK_TREE_LEVELS; ++l) {
+        out->level_nodes[l] = count;
+        out->tree_base[l] = d.tree_base[l];
+        if (l == d.tree_top) out->top_family = count;
+        count = (count + 3) / 4;
+    }
+    std::vector<double> tf((size_t)d.tree_leaves * NK_TREE_LEAF_DOUBLES);
+    NK_HIP(hipMemcpy(tf.data(), d.tree_faces, tf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int leaf = 0; leaf < d.tree_leaves; ++leaf) {
+        float fb[24];
+        memcpy(fb, &tf[(size_t)leaf * NK_TREE_LEAF_DOUBLES], sizeof(fb));
+        for (int c = 0; c < 4; ++c) {
+            if (fb[6 * c] > fb[6 * c + 3]) ++out->pad_slots; else ++out->references;
+        }
+        if (leaf_boxes) memcpy(leaf_boxes + (size_t)leaf * 24, fb, sizeof(fb));
+    }
+    if (family_boxes)
+        NK_HIP(hipMemcpy(family_boxes, d.tree_boxes, (size_t)d.tree_nfam * NK_TREE_FAMILY_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+    return NK_OK;
+}
 int nk_classify(nk_ctx *ctx, int64_t n, const double *x, int32_t *id) {
     NK_ARG(ctx && ctx->have_sv && n > 0 && x && id, "nk_classify: bad arguments");
     NK_HIP(hipSetDevice(ctx->device));

@@ -2383,6 +2383,30 @@ __global__ __launch_bounds__(NK_WG) void k_tap_find_boundary(NkDev d, int64_t n,
     tc[i] = t; fc[i] = f;
     for (int k = 0; k < 3; ++k) xc[3 * i + k] = x[3 * i + k] + t * v[3 * i + k];
 }
+// the same for rays that start on a named facet: the skip is formed exactly as k_sweep forms it for an entering particle
+// (nk_tree_skip with the facet's centroid and normal), then handed to the cast.  from_facet outside [0, Fc): no skip.
+// skipped[i] = 1 where the walk skipped the nodes that hold only that facet's faces (never on a mesh whose tables sit in LDS).
+template <int GEOM>
+__global__ __launch_bounds__(NK_WG) void k_tap_find_boundary_from(NkDev d, int64_t n, const double *x, const double *v, const int32_t *from_facet,
+                                                                  double *xc, double *tc, int32_t *fc, int32_t *skipped) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    NkLds L;
+    nk_lds_setup<GEOM, 0>(d, smem, L);
+    int64_t i = (int64_t)blockIdx.x * NK_WG + threadIdx.x;
+    if (i >= n) return;
+    const double x0 = x[3 * i], y0 = x[3 * i + 1], z0 = x[3 * i + 2], vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
+    const int rf = from_facet[i];
+    int skip = NK_TREE_NO_SKIP;
+    if (GEOM == 2 && d.NG > 0 && rf >= 0 && rf < d.Fc) {
+        const NkFacet &fq = d.facets[rf];
+        skip = nk_tree_skip(d, rf, fq.cx, fq.cy, fq.cz, fq.nx, fq.ny, fq.nz, x0, y0, z0, vx, vy, vz);
+    }
+    double t; int f;
+    NK_RAY(GEOM, d, L, skip, x0, y0, z0, vx, vy, vz, t, f);
+    tc[i] = t; fc[i] = f;
+    skipped[i] = (skip != NK_TREE_NO_SKIP && skip == rf) ? 1 : 0;
+    xc[3 * i] = x0 + t * vx; xc[3 * i + 1] = y0 + t * vy; xc[3 * i + 2] = z0 + t * vz;
+}
 NK_KERNEL_LINKAGE __global__ __launch_bounds__(NK_WG) void k_tap_classify(NkDev d, int64_t n, const double *x, int32_t *id) {
     extern __shared__ __align__(16) unsigned char smem[];
     NkLds L;

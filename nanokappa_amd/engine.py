@@ -84,7 +84,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_reservoirs', 'nk_set_rough', 'nk_set_params', 'nk_reserve', 'nk_upload_particles',
            'nk_init_boundaries', 'nk_step', 'nk_download_particles', 'nk_get_subvol_temperature',
            'nk_set_subvol_temperature', 'nk_get_step', 'nk_get_timing', 'nk_comm_unique_id', 'nk_comm_init',
-           'nk_find_boundary', 'nk_classify', 'nk_box_hit', 'nk_eval', 'nk_mode_segments', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
+           'nk_find_boundary', 'nk_find_boundary_from', 'nk_tree_info', 'nk_classify', 'nk_box_hit', 'nk_eval', 'nk_mode_segments', 'nk_reflect', 'nk_uniform2', 'nk_calibrate_stream',
            'nk_specular_begin', 'nk_specular_pairs', 'nk_specular_end', 'nk_rough_begin', 'nk_rough_pairs', 'nk_rough_finish',
            'nk_rough_download', 'nk_build_enter_prob', 'nk_init_particles', 'nk_tally_state', 'nk_kspec_begin', 'nk_kspec_pairs',
            'nk_rough_finish_k', 'nk_mesh_crossings', 'nk_comm_info', 'nk_comm_allreduce', 'nk_set_bands', 'nk_get_band_rows',
@@ -118,6 +118,12 @@ class nk_modes(C.Structure):
 class nk_modes_report(C.Structure):
     _fields_ = [('every', C.c_int32), ('k_E', C.c_int32), ('B_E', C.c_double), ('capacity', C.c_int64), ('bytes', C.c_int64),
                 ('owner_path', C.c_int32), ('on', C.c_int32)]
+
+
+class nk_tree_report(C.Structure):
+    _fields_ = [('NG', C.c_int32), ('tree_top', C.c_int32), ('level_nodes', C.c_int32 * 8), ('tree_base', C.c_int32 * 8),
+                ('top_family', C.c_int32), ('tree_leaves', C.c_int32), ('references', C.c_int32), ('pad_slots', C.c_int32),
+                ('n_families', C.c_int32), ('pad_', C.c_int32), ('tree_bound', C.c_double)]
 
 
 class nk_solid_report(C.Structure):
@@ -221,6 +227,8 @@ def load_library():
     L.nk_comm_info.argtypes = [C.c_void_p, C.POINTER(nk_comm_report)]
     L.nk_comm_allreduce.argtypes = [C.c_void_p, c_dp, C.c_int64]
     L.nk_find_boundary.argtypes = [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, c_ip]
+    L.nk_find_boundary_from.argtypes = [C.c_void_p, C.c_int64, c_dp, c_dp, c_ip, c_dp, c_dp, c_ip, c_ip]
+    L.nk_tree_info.argtypes = [C.c_void_p, C.POINTER(nk_tree_report), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.nk_classify.argtypes = [C.c_void_p, C.c_int64, c_dp, c_ip]
     L.nk_box_hit.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_dp, c_dp, c_dp, c_ip]
     L.nk_eval.argtypes = [C.c_void_p, C.c_int32, C.c_int64, c_dp, c_ip, c_dp]
@@ -1026,12 +1034,40 @@ class Engine(object):
                     pci_bus_id=r.pci_bus_id.decode(errors='replace'))
 
     # -------------------------------------------------------------------- taps
-    def find_boundary(self, x, v):
+    def find_boundary(self, x, v, from_facet=None):
+        """(xc, tc, fc) of the rays (x, v).  from_facet [n]: the facet every ray starts on (-1: none), for which the walk of the
+        face tree forms its facet skip as the sweep does; then also `skipped` [n] (1 where the skip engaged)."""
         x, v = _d(x), _d(v)
         n = x.shape[0]
         xc, tc, fc = np.zeros((n, 3)), np.zeros(n), np.zeros(n, dtype=np.int32)
-        self._ck(self.L.nk_find_boundary(self.h, n, _p(x), _p(v), _p(xc), _p(tc), _p(fc, c_ip)), 'nk_find_boundary')
-        return xc, tc, fc
+        if from_facet is None:
+            self._ck(self.L.nk_find_boundary(self.h, n, _p(x), _p(v), _p(xc), _p(tc), _p(fc, c_ip)), 'nk_find_boundary')
+            return xc, tc, fc
+        ff, sk = _i(np.broadcast_to(np.asarray(from_facet, dtype=np.int32), (n,))), np.zeros(n, dtype=np.int32)
+        self._ck(self.L.nk_find_boundary_from(self.h, n, _p(x), _p(v), _p(ff, c_ip), _p(xc), _p(tc), _p(fc, c_ip), _p(sk, c_ip)),
+                 'nk_find_boundary_from')
+        return xc, tc, fc, sk
+
+    def tree_info(self, boxes=False):
+        """The face tree of the mesh (nk_tree_info): NG, tree_top, level_nodes [tree_top + 1], top_family, tree_leaves, references,
+        pad_slots, tree_bound, tree_base.  boxes=True adds family_boxes [levels][nodes incl. padding, 6] (lo(3), hi(3) as float32;
+        padding boxes have lo > hi) and leaf_boxes [tree_leaves, 4, 6].  Reads only."""
+        r = nk_tree_report()
+        self._ck(self.L.nk_tree_info(self.h, C.byref(r), None, None), 'nk_tree_info')
+        nl = int(r.tree_top) + 1 if r.NG else 0
+        out = dict(NG=int(r.NG), tree_top=int(r.tree_top), level_nodes=[int(r.level_nodes[l]) for l in range(nl)],
+                   tree_base=[int(r.tree_base[l]) for l in range(nl)], top_family=int(r.top_family), tree_leaves=int(r.tree_leaves),
+                   references=int(r.references), pad_slots=int(r.pad_slots), n_families=int(r.n_families), tree_bound=float(r.tree_bound))
+        if boxes and r.NG:
+            fb = np.zeros(int(r.n_families) * 24, dtype=np.float32)
+            lb = np.zeros(int(r.tree_leaves) * 24, dtype=np.float32)
+            c_fp = C.POINTER(C.c_float)
+            self._ck(self.L.nk_tree_info(self.h, C.byref(r), _p(fb, c_fp), _p(lb, c_fp)), 'nk_tree_info')
+            fb = fb.reshape(-1, 6)
+            ends = out['tree_base'][1:] + [fb.shape[0]]
+            out['family_boxes'] = [fb[a:b].copy() for a, b in zip(out['tree_base'], ends)]
+            out['leaf_boxes'] = lb.reshape(-1, 4, 6)
+        return out
 
     def classify(self, x):
         x = _d(x)

@@ -339,7 +339,17 @@ def plane_times(g, x, v, tol=TOL):
     return t, np.asarray(inv).reshape(-1)
 
 
-def all_faces_cast(g, x, v, tol=TOL):
+def all_faces_cast(g, x, v, tol=TOL, chunk=1024):
+    """_all_faces_block on `chunk` rays at a time (it holds n x F x 3 arrays); every ray is evaluated on its own, so the result
+    does not depend on the chunk."""
+    x, v = np.asarray(x, dtype=float), np.asarray(v, dtype=float)
+    if x.shape[0] <= chunk:
+        return _all_faces_block(g, x, v, tol)
+    parts = [_all_faces_block(g, x[a:a + chunk], v[a:a + chunk], tol) for a in range(0, x.shape[0], chunk)]
+    return {k: (sum((q[k] for q in parts), []) if k == 'adm' else np.concatenate([q[k] for q in parts])) for k in parts[0]}
+
+
+def _all_faces_block(g, x, v, tol=TOL):
     """Mesh.find_boundary in float64 with the arithmetic of oracle/nk_oracle.c find_boundary_one (products summed left to
     right, no fused multiply-adds, barycentric coordinates by Cramer's rule), returning EVERY passing face:
     T [n, F] (inf where a face does not pass), and per ray tc, the first face of the minimum, its facet, the admissible set of
@@ -423,84 +433,369 @@ def _aim(rng, target, normal, scale=0.125):
     return x, (target - x) * scale / h * 8.0
 
 
+def ray_families(g, seed, ngen, planetie):
+    """The ray families of any mesh table dict g: generic interior rays (ngen of them), starts on the surface and outside,
+    axis-parallel rays with zeros of either sign, rays through quad diagonals, edges and vertices, and -- `planetie` -- rays with two
+    planes tied for the smallest t.  Returns (x, v, {family: index array}) and the generator, for families that follow."""
+    rng = np.random.default_rng(seed)
+    V_, faces = np.asarray(g['vertices'], dtype=float), np.asarray(g['faces'], dtype=int)
+    n_ = np.asarray(g['face_normals'], dtype=float)
+    b = np.asarray(g['bounds'], dtype=float)
+    X, V, fam = [], [], {}
+
+    def add(key, x, v):
+        start = sum(a.shape[0] for a in X)
+        X.append(np.atleast_2d(x)), V.append(np.atleast_2d(v))
+        fam[key] = np.arange(start, start + X[-1].shape[0])
+    add('generic', sample_inside(g, ngen, rng), rng.normal(size=(ngen, 3)) * 40.0)
+    # starts on the surface: first hits of other rays
+    x0, v0 = sample_inside(g, 400, rng), rng.normal(size=(400, 3)) * 40.0
+    r0 = all_faces_cast(g, x0, v0)
+    xs = (x0 + r0['tc'][:, None] * v0)[r0['hit']]
+    add('surface', xs, rng.normal(size=xs.shape) * 40.0)
+    # starts outside: aimed at the body (hits) and away from it or past it (misses)
+    xo = b[1] + 7.0 + 20.0 * rng.random((200, 3))
+    xo[::2] = b[0] - 7.0 - 20.0 * rng.random((100, 3))
+    vo = rng.normal(size=(200, 3)) * 40.0
+    vo[:120] = (sample_inside(g, 120, rng) - xo[:120]) * 0.0625
+    add('outside', xo, vo)
+    # axis-parallel rays, zeros of either sign
+    va = np.zeros((240, 3))
+    for i in range(240):
+        va[i] = [0.0, -0.0, 0.0][i % 3:] + [0.0, -0.0, 0.0][:i % 3]
+        va[i, i % 3] = 40.0 if (i // 3) % 2 else -40.0
+    add('axis', sample_inside(g, 240, rng), va)
+    # through the shared diagonal of two coplanar triangles / an edge between two faces of different planes / a vertex
+    edges = _shared_edges(g)
+    for key, want, per in (('diagonal', True, 6), ('edge', False, 4)):
+        xs_, vs_ = [], []
+        count = sum(1 for e in edges if e[4] == want)
+        per = max(per, -(-120 // max(count, 1)))                 # at least 120 rays per family
+        for (i, j, a, bb, cop) in edges:
+            if cop != want:
+                continue
+            for _ in range(per):
+                s = 0.1 + 0.8 * rng.random()
+                x, v = _aim(rng, V_[a] + s * (V_[bb] - V_[a]), n_[i] + n_[j])
+                xs_.append(x), vs_.append(v)
+        if xs_:
+            add(key, np.array(xs_), np.array(vs_))
+    xs_, vs_ = [], []
+    used = np.unique(faces)
+    for vi in used:
+        inc = np.nonzero((faces == vi).any(axis=1))[0]
+        for _ in range(max(3, -(-120 // used.shape[0]))):
+            x, v = _aim(rng, V_[vi], n_[inc].sum(axis=0) if np.linalg.norm(n_[inc].sum(axis=0)) > 1e-6 else n_[inc[0]])
+            xs_.append(x), vs_.append(v)
+    add('vertex', np.array(xs_), np.array(vs_))
+    if planetie:
+        # two planes tied for the smallest t, bit for bit: a seeded search among many edge-aimed rays, on the planes alone
+        E = np.array([(i, j, a, bb) for (i, j, a, bb, cop) in edges if not cop])
+        pick = E[rng.integers(0, E.shape[0], 40000)]
+        tgt = V_[pick[:, 2]] + (0.1 + 0.8 * rng.random((40000, 1))) * (V_[pick[:, 3]] - V_[pick[:, 2]])
+        nrm = n_[pick[:, 0]] + n_[pick[:, 1]]
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        side = rng.normal(size=(40000, 3))
+        side -= nrm * np.sum(side * nrm, axis=1, keepdims=True)
+        h = 0.5 + 2.5 * rng.random((40000, 1))
+        xs_ = tgt - nrm * h + 0.3 * h * rng.random((40000, 1)) * side / np.linalg.norm(side, axis=1, keepdims=True)
+        vs_ = (tgt - xs_) / h
+        tp = np.sort(plane_times(g, xs_, vs_)[0], axis=1)
+        tie = np.nonzero(np.isfinite(tp[:, 0]) & (tp[:, 0] == tp[:, 1]))[0][:300]
+        add('planetie', xs_[tie], vs_[tie])
+    return np.concatenate(X), np.concatenate(V), fam, rng
+
+
+LDS_SEEDS = {'box200ttp': 5, 'cyl': 6, 'corrugated': 7, 'castle': 8}
+
+
 def lds_families(name):
     """Ray families on a small mesh (tables in LDS): {family: index array}, x, v, and the all-faces reference."""
     def make():
         g = lds_mesh(name)
-        rng = np.random.default_rng({'box200ttp': 5, 'cyl': 6, 'corrugated': 7, 'castle': 8}[name])
-        V_, faces = np.asarray(g['vertices'], dtype=float), np.asarray(g['faces'], dtype=int)
-        n_ = np.asarray(g['face_normals'], dtype=float)
-        b = np.asarray(g['bounds'], dtype=float)
-        X, V, fam = [], [], {}
-
-        def add(key, x, v):
-            start = sum(a.shape[0] for a in X)
-            X.append(np.atleast_2d(x)), V.append(np.atleast_2d(v))
-            fam[key] = np.arange(start, start + X[-1].shape[0])
-        ngen = 3000 if name in NONCONVEX_ARGS else 600
-        add('generic', sample_inside(g, ngen, rng), rng.normal(size=(ngen, 3)) * 40.0)
-        # starts on the surface: first hits of other rays
-        x0, v0 = sample_inside(g, 400, rng), rng.normal(size=(400, 3)) * 40.0
-        r0 = all_faces_cast(g, x0, v0)
-        xs = (x0 + r0['tc'][:, None] * v0)[r0['hit']]
-        add('surface', xs, rng.normal(size=xs.shape) * 40.0)
-        # starts outside: aimed at the body (hits) and away from it or past it (misses)
-        xo = b[1] + 7.0 + 20.0 * rng.random((200, 3))
-        xo[::2] = b[0] - 7.0 - 20.0 * rng.random((100, 3))
-        vo = rng.normal(size=(200, 3)) * 40.0
-        vo[:120] = (sample_inside(g, 120, rng) - xo[:120]) * 0.0625
-        add('outside', xo, vo)
-        # axis-parallel rays, zeros of either sign
-        va = np.zeros((240, 3))
-        for i in range(240):
-            va[i] = [0.0, -0.0, 0.0][i % 3:] + [0.0, -0.0, 0.0][:i % 3]
-            va[i, i % 3] = 40.0 if (i // 3) % 2 else -40.0
-        add('axis', sample_inside(g, 240, rng), va)
-        # through the shared diagonal of two coplanar triangles / an edge between two faces of different planes / a vertex
-        edges = _shared_edges(g)
-        for key, want, per in (('diagonal', True, 6), ('edge', False, 4)):
-            xs_, vs_ = [], []
-            count = sum(1 for e in edges if e[4] == want)
-            per = max(per, -(-120 // max(count, 1)))                 # at least 120 rays per family
-            for (i, j, a, bb, cop) in edges:
-                if cop != want:
-                    continue
-                for _ in range(per):
-                    s = 0.1 + 0.8 * rng.random()
-                    x, v = _aim(rng, V_[a] + s * (V_[bb] - V_[a]), n_[i] + n_[j])
-                    xs_.append(x), vs_.append(v)
-            if xs_:
-                add(key, np.array(xs_), np.array(vs_))
-        xs_, vs_ = [], []
-        used = np.unique(faces)
-        for vi in used:
-            inc = np.nonzero((faces == vi).any(axis=1))[0]
-            for _ in range(max(3, -(-120 // used.shape[0]))):
-                x, v = _aim(rng, V_[vi], n_[inc].sum(axis=0) if np.linalg.norm(n_[inc].sum(axis=0)) > 1e-6 else n_[inc[0]])
-                xs_.append(x), vs_.append(v)
-        add('vertex', np.array(xs_), np.array(vs_))
-        if name in NONCONVEX_ARGS:
-            # two planes tied for the smallest t, bit for bit: a seeded search among many edge-aimed rays, on the planes alone
-            E = np.array([(i, j, a, bb) for (i, j, a, bb, cop) in edges if not cop])
-            pick = E[rng.integers(0, E.shape[0], 40000)]
-            tgt = V_[pick[:, 2]] + (0.1 + 0.8 * rng.random((40000, 1))) * (V_[pick[:, 3]] - V_[pick[:, 2]])
-            nrm = n_[pick[:, 0]] + n_[pick[:, 1]]
-            nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-            side = rng.normal(size=(40000, 3))
-            side -= nrm * np.sum(side * nrm, axis=1, keepdims=True)
-            h = 0.5 + 2.5 * rng.random((40000, 1))
-            xs_ = tgt - nrm * h + 0.3 * h * rng.random((40000, 1)) * side / np.linalg.norm(side, axis=1, keepdims=True)
-            vs_ = (tgt - xs_) / h
-            tp = np.sort(plane_times(g, xs_, vs_)[0], axis=1)
-            tie = np.nonzero(np.isfinite(tp[:, 0]) & (tp[:, 0] == tp[:, 1]))[0][:300]
-            add('planetie', xs_[tie], vs_[tie])
-        x, v = np.concatenate(X), np.concatenate(V)
+        x, v, fam, _ = ray_families(g, LDS_SEEDS[name], 3000 if name in NONCONVEX_ARGS else 600, name in NONCONVEX_ARGS)
         return dict(x=x, v=v, fam=fam, ref=all_faces_cast(g, x, v))
     return cached(('lds_fam', name), make)
 
 
+# ------------------------------------------------------------- meshes cast through the face tree
+# More than 256 faces (NK_LDS_FACES): the tables stay in global memory and every cast walks the face tree.  The smallest meshes
+# that reach every part of it: wire72 a tree of several levels over 288 faces with fan caps; star adds diagonal slivers and a
+# non-convex section; longwire has side triangles of 13 A x 60 000 A, every one split into several references, and coordinates
+# up to 6e4, where a float's ulp is 0.004 A.
+TREE_BOUNDS = ['--bound_pos', 'relative', '0.5', '0.5', '0', '0.5', '0.5', '1', '--bound_cond', 'T', 'T', 'R',
+               '--bound_values', '302', '298', '5']
+TREE_ARGS = {
+    'wire72': ['--geometry', 'cylinder', '--dimensions', '500', '100', '72', '--subvolumes', 'slice', '10', '2'],
+    'star': ['--geometry', 'star', '--dimensions', '600', '200', '90', '72', '--subvolumes', 'slice', '4', '2'],
+    'longwire': ['--geometry', 'cylinder', '--dimensions', '60000', '150', '72', '--subvolumes', 'slice', '10', '2'],
+}
+TREE_SEED = 6
+TREE_NGEN = 600
+SPEEDS = (1e-3, 1.0, 40.0, 1e4)
+TINY = (0.0, 4.9e-324, 1e-310, 1e-40, 1e-25, 1e-12, 1e-6)
+
+
+def tree_case(name):
+    """case_from_args of a tree-sized mesh: ['mesh'] the tables, ['geo'].mesh the package's Mesh."""
+    return cached(('tree_case', name), lambda: case_from_args(TREE_ARGS[name] + TREE_BOUNDS + COMMON_ARGS))
+
+
+def tree_mesh(name):
+    return tree_case(name)['mesh']
+
+
+def side_faces(g):
+    """Faces of the facets that are no end cap (caps: facet normal along the wire's axis z)."""
+    nz = np.abs(np.asarray(g['facets_normal'], dtype=float)[:, 2])
+    return np.nonzero(nz[np.asarray(g['face_facets'], dtype=int)] < 0.5)[0]
+
+
+def cap_facets(g):
+    """The two end caps: facets whose normal is +-e_z."""
+    return [int(c) for c in np.nonzero(np.abs(np.asarray(g['facets_normal'], dtype=float)[:, 2]) == 1.0)[0]]
+
+
+def _sliver_rays(g, rng):
+    """Hits spread along the whole length of long side faces: towards points at fractions 2^-k, 1 - 2^-k and random ones of a
+    face's longest edge -- on the edge itself (the diagonal it shares with its coplanar neighbour) and moved into the face --
+    and rays nearly parallel to the axis that travel thousands of angstrom before they hit."""
+    V_, faces = np.asarray(g['vertices'], dtype=float), np.asarray(g['faces'], dtype=int)
+    n_ = np.asarray(g['face_normals'], dtype=float)
+    X, V = [], []
+    side = side_faces(g)
+    for f in rng.choice(side, size=min(48, side.shape[0]), replace=False):
+        P = V_[faces[f]]
+        e = int(np.argmax([np.linalg.norm(P[(k + 1) % 3] - P[k]) for k in range(3)]))
+        a, b, c = P[e], P[(e + 1) % 3], P[(e + 2) % 3]
+        fr = [2.0 ** -k for k in range(1, 7)] + [1.0 - 2.0 ** -k for k in range(2, 7)] + list(rng.random(5))
+        for i, s in enumerate(fr):
+            tgt = a + s * (b - a)
+            if i % 2:
+                tgt = tgt + (0.05 + 0.6 * rng.random()) * (c - tgt)
+            x, v = _aim(rng, tgt, n_[f])
+            X.append(x), V.append(v)
+    x0 = sample_inside(g, 7 * 24, rng)
+    for i in range(x0.shape[0]):
+        q = 1.0 - 10.0 ** -(3 + i % 7)                              # |v_z| / |v|
+        phi = 2.0 * np.pi * rng.random()
+        s = np.sqrt((1.0 - q) * (1.0 + q))
+        X.append(x0[i]), V.append(40.0 * np.array([s * np.cos(phi), s * np.sin(phi), q if (i // 7) % 2 else -q]))
+    return np.array(X), np.array(V)
+
+
+def _tiny_rays(g, rng):
+    """One component +-40, each of the others from +-TINY: every pair of values and signs once per axis and direction."""
+    vals = [sg * t for t in TINY for sg in (1.0, -1.0)]
+    V = []
+    for a in range(3):
+        for big in (40.0, -40.0):
+            for p in vals:
+                for q in vals:
+                    v = np.array([p, q, q])
+                    v[(a + 1) % 3], v[(a + 2) % 3], v[a] = p, q, big
+                    V.append(v)
+    V = np.array(V)
+    return sample_inside(g, V.shape[0], rng), V
+
+
+def _far_rays(g, rng, n=480):
+    """Starts 1e3 .. 1e6 A from the body (where a float's ulp reaches 0.06 A: the |x| term of the slab test's widening), flying at
+    |v| = 40 towards interior points, points of shared edges and vertices: near-ties at the end of a long flight, where the float
+    tmax is all that stands between a worse hit found first and the better one."""
+    V_, faces = np.asarray(g['vertices'], dtype=float), np.asarray(g['faces'], dtype=int)
+    edges = _shared_edges(g)
+    m = n // 3
+    e = [edges[i] for i in rng.integers(0, len(edges), m)]
+    s = 0.1 + 0.8 * rng.random((m, 1))
+    on_edge = np.array([V_[a] for (_, _, a, _, _) in e]) + s * np.array([V_[b] - V_[a] for (_, _, a, b, _) in e])
+    tgt = np.concatenate([sample_inside(g, n - 2 * m, rng), on_edge, V_[rng.choice(np.unique(faces), m)]])
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    dist = 10.0 ** (3.0 + 3.0 * rng.random((n, 1)))
+    x = tgt + dist * u
+    return x, (tgt - x) * (40.0 / dist)
+
+
+def subtiny_rays(g, seed=TREE_SEED):
+    """20 rays whose every component lies below 1e-30 in magnitude, in unequal ratio (1 : 3 : 0 and the like): all their 1 / v
+    clamp to the same NK_RAY_BIG.  Outside the cast's stated domain (largest |v_a| >= 1e-25, nk_device.h); kept for probes."""
+    rng = np.random.default_rng(seed + 1000)
+    V = []
+    for i in range(20):
+        v = np.array([1.0, 3.0, 0.0, 1.0, -7.0, 2.0][i % 4:i % 4 + 3]) * 10.0 ** -(31 + i % 6)
+        V.append(np.roll(v, i % 3) * (1.0 if i % 2 else -1.0))
+    return sample_inside(g, 20, rng), np.array(V)
+
+
+def tree_families(name):
+    """ray_families on a tree-sized mesh plus the families of the tree's own filters: `speed` (|v| over seven orders of magnitude:
+    tmax), `tiny` (components that are zero, denormal or so small that (float)(1 / v) overflows: the NK_RAY_BIG clamp), on
+    longwire `sliver`, and `far` (starts up to 1e6 A away: the widening's |x| term, near-ties after long flights).  {x, v, fam, ref} like lds_families.  (`boxwall` needs the boxes of the device's tree: boxwall_rays.)"""
+    def make():
+        g = tree_mesh(name)
+        x, v, fam, rng = ray_families(g, TREE_SEED, TREE_NGEN, False)
+        X, V = [x], [v]
+
+        def add(key, xs, vs):
+            start = sum(a.shape[0] for a in X)
+            X.append(xs), V.append(vs)
+            fam[key] = np.arange(start, start + xs.shape[0])
+        gi = fam['generic']
+        d = v[gi] / np.linalg.norm(v[gi], axis=1, keepdims=True)
+        add('speed', x[gi], d * np.array(SPEEDS)[np.arange(gi.shape[0]) % len(SPEEDS), None])
+        add('tiny', *_tiny_rays(g, rng))
+        if name == 'longwire':
+            add('sliver', *_sliver_rays(g, rng))
+        add('far', *_far_rays(g, rng))
+        x, v = np.concatenate(X), np.concatenate(V)
+        return dict(x=x, v=v, fam=fam, ref=all_faces_cast(g, x, v))
+    return cached(('tree_fam', name), make)
+
+
+def decided(ref):
+    """Where the facet must be the reference's own rather than any member of the admissible set: one admissible facet, an exact
+    tie between faces (then the lowest face index), or a miss.  Returns (decided, exact_tie)."""
+    one = np.array([len(a) == 1 for a in ref['adm']])
+    exact_tie = (ref['T'] == ref['tc'][:, None]).sum(axis=1) > 1
+    return one | exact_tie | ~ref['hit'], exact_tie & ref['hit']
+
+
+def boxwall_rays(g, info, seed=TREE_SEED, nboxes=40):
+    """Rays at the walls of the tree's own boxes (Engine.tree_info(boxes=True)): about `nboxes` boxes over all levels, leaf face
+    boxes included.  Per wall: two rays INSIDE the wall plane (the coordinate equals the wall's float exactly, v_a = +0.0 and
+    -0.0, the rest random) and two that start on the wall and fly perpendicular to it, either way; per corner rays through it along
+    (+-1, +-1, +-1) 2^k.  The starts spread over the box and a margin around it: some lie in the solid, some outside."""
+    rng = np.random.default_rng(seed + 77)
+    boxes = []
+    per = max(2, nboxes // (len(info['family_boxes']) + 1))
+    for lv in list(info['family_boxes']) + [info['leaf_boxes'].reshape(-1, 6)]:
+        real = lv[lv[:, 0] <= lv[:, 3]].astype(np.float64)
+        boxes += list(real[rng.choice(real.shape[0], size=min(per, real.shape[0]), replace=False)])
+    X, V = [], []
+    for B in boxes:
+        lo, hi = B[:3], B[3:]
+        ext = hi - lo
+        for a in range(3):
+            for wall in (lo[a], hi[a]):
+                for z in (0.0, -0.0):
+                    x = lo - 0.2 * ext + 1.4 * ext * rng.random(3)
+                    v = rng.normal(size=3) * 40.0
+                    x[a], v[a] = wall, z
+                    X.append(x), V.append(v)
+                for sg in (40.0, -40.0):
+                    x = lo + ext * rng.random(3)
+                    x[a] = wall
+                    v = np.zeros(3)
+                    v[a] = sg
+                    X.append(x), V.append(v)
+        for c in CORNERS:
+            corner = np.array([hi[k] if c[k] else lo[k] for k in range(3)])
+            for k in (-2, 5):
+                d = rng.choice([-1.0, 1.0], size=3)
+                X.append(corner - 2.0 * d), V.append(d * 2.0 ** k)
+    x, v = np.array(X), np.array(V)
+    return dict(x=x, v=v, nboxes=len(boxes), ref=all_faces_cast(g, x, v))
+
+
+# the facet skip (nk_tree_skip, nk_device.h) restated
+def facet_skip_tables(g):
+    """Per facet (dn, dk) as nk_set_mesh forms them: the largest component of n_face - n_facet and the largest
+    |n_face . centroid + k_face| over the facet's faces; dn = 1e300 ("never") for facets of fewer than 16 faces."""
+    n_, k_ = np.asarray(g['face_normals'], dtype=float), np.asarray(g['face_k'], dtype=float)
+    ff = np.asarray(g['face_facets'], dtype=int)
+    fn, fc = np.asarray(g['facets_normal'], dtype=float), np.asarray(g['facet_centroid'], dtype=float)
+    Fc = fn.shape[0]
+    dn, dk = np.zeros(Fc), np.zeros(Fc)
+    np.maximum.at(dn, ff, np.abs(n_ - fn[ff]).max(axis=1))
+    c = fc[ff]
+    np.maximum.at(dk, ff, np.abs(((n_[:, 0] * c[:, 0] + n_[:, 1] * c[:, 1]) + n_[:, 2] * c[:, 2]) + k_))
+    dn[np.bincount(ff, minlength=Fc) < 16] = 1e300
+    return dn, dk
+
+
+def tree_skip_rule(g, from_facet, x, v, tol=TOL):
+    """nk_tree_skip: skip where (dist + dn r + dk) 1.000001 + 1e-300 < tol / 2 (|v . n| - dn |v|_1).  Returns (skip, lhs, rhs);
+    names outside [0, Fc) never skip (lhs = inf)."""
+    fn, fc = np.asarray(g['facets_normal'], dtype=float), np.asarray(g['facet_centroid'], dtype=float)
+    dn, dk = facet_skip_tables(g)
+    ff = np.asarray(from_facet, dtype=int)
+    ok = (ff >= 0) & (ff < fn.shape[0])
+    f = np.where(ok, ff, 0)
+    r_ = x - fc[f]
+    n = fn[f]
+    with np.errstate(all='ignore'):
+        dist = np.abs((r_[:, 0] * n[:, 0] + r_[:, 1] * n[:, 1]) + r_[:, 2] * n[:, 2])
+        r1, vv = np.abs(r_).sum(axis=1), np.abs(v).sum(axis=1)
+        vn = np.abs((v[:, 0] * n[:, 0] + v[:, 1] * n[:, 1]) + v[:, 2] * n[:, 2])
+        lhs = np.where(ok, (dist + dn[f] * r1 + dk[f]) * 1.000001 + 1e-300, np.inf)
+        rhs = 0.5 * tol * (vn - dn[f] * vv)
+    return lhs < rhs, lhs, rhs
+
+
+SKIP_C = (0.125, 0.499, 0.501, 1.0, 4.0, 1e4)
+SKIP_GRAZE = (0.0, 1e-9, 1e-6, 1e-3)
+
+
+def skip_families(name):
+    """Rays for the facet skip on a mesh with fan caps: {x, v, from_facet, fam}.
+    (a) 1500 starts on each cap (Mesh.sample_surface), random inward directions; (b) starts of (a) moved along the normal by
+    +-c tol |v.n|, c in SKIP_C: the cap's own t straddles tol / 2 and tol; (c) grazing and outward rays, |v.n| / |v| in SKIP_GRAZE
+    of either sign; (d) starts on the cap's rim vertices and rim edges; (e) starts of (a) under wrong names: the other cap, a side
+    facet, -1 and Fc."""
+    def make():
+        ct = tree_case(name)
+        g, mesh = ct['mesh'], ct['geo'].mesh
+        rng = np.random.default_rng(TREE_SEED + 200)
+        fn = np.asarray(g['facets_normal'], dtype=float)
+        V_, faces, ff = np.asarray(g['vertices'], dtype=float), np.asarray(g['faces'], dtype=int), np.asarray(g['face_facets'], dtype=int)
+        caps = cap_facets(g)
+        assert len(caps) == 2
+        side = int(np.nonzero(np.abs(fn[:, 2]) < 0.5)[0][0])
+        X, V, FF, fam = [], [], [], {}
+
+        def add(key, xs, vs, names):
+            start = sum(a.shape[0] for a in X)
+            X.append(xs), V.append(vs), FF.append(np.broadcast_to(np.asarray(names, dtype=np.int32), (xs.shape[0],)).copy())
+            fam[key] = np.concatenate([fam.get(key, np.zeros(0, dtype=int)), np.arange(start, start + xs.shape[0])])
+
+        def inward(n, m):
+            v = rng.normal(size=(m, 3)) * 40.0
+            vn = v @ n
+            return v - np.outer(vn + np.abs(vn), n)                  # v.n -> -|v.n|
+        for ci, cap in enumerate(caps):
+            n = fn[cap]
+            xa = mesh.sample_surface(1500, facets=[cap], rng=rng)
+            va = inward(n, 1500)
+            add('a', xa, va, cap)
+            xb, vb = xa[:100], va[:100]
+            for c in SKIP_C:
+                for sg in (1.0, -1.0):
+                    add('b', xb + np.outer(sg * c * TOL * np.abs(vb @ n), n), vb, cap)
+            t1 = np.cross(n, [1.0, 0.0, 0.0])
+            t2 = np.cross(n, t1)
+            for q in SKIP_GRAZE:
+                for sg in (1.0, -1.0):
+                    phi = 2.0 * np.pi * rng.random(50)
+                    tang = np.outer(np.cos(phi), t1) + np.outer(np.sin(phi), t2)
+                    add('c', xa[200:250], 40.0 * (np.sqrt((1.0 - q) * (1.0 + q)) * tang + sg * q * n), cap)
+            add('c', xa[250:400], -inward(n, 150), cap)                     # outward
+            cf = faces[ff == cap]
+            vid, cnt = np.unique(cf, return_counts=True)
+            rim = vid[cnt < cnt.max()] if cnt.max() > 2 else vid         # (a fan's centre belongs to every face of the cap)
+            add('d', V_[rim], inward(n, rim.shape[0]), cap)
+            re = np.array([sorted(e) for tri in cf for e in ((tri[0], tri[1]), (tri[1], tri[2]), (tri[2], tri[0]))
+                           if e[0] in rim and e[1] in rim])
+            s = rng.random((re.shape[0], 1))
+            add('d', V_[re[:, 0]] + s * (V_[re[:, 1]] - V_[re[:, 0]]), inward(n, re.shape[0]), cap)
+            for wrong in (caps[1 - ci], side, -1, fn.shape[0]):
+                add('e', xa[:200], va[:200], wrong)
+        return dict(x=np.concatenate(X), v=np.concatenate(V), from_facet=np.concatenate(FF), fam=fam, caps=caps)
+    return cached(('skip_fam', name), make)
+
+
 # ------------------------------------------------------------------------------ slice lookups
-S_MAX_TAP = 160        # nk_set_subvolumes takes S <= 512, and the taps' LDS tables fit the default 64 KB up to S = 180
+S_MAX_TAP = 160       # nk_set_subvolumes takes S <= 512, and the taps' LDS tables fit the default 64 KB up to S = 180
 
 
 def slice_sets():
