@@ -8,6 +8,8 @@
 #include <string.h>
 #include <algorithm>
 #include <functional>
+#include <map>
+#include <mutex>
 #include <queue>
 #include <string>
 #include <type_traits>
@@ -68,7 +70,7 @@ struct nk_ctx {
     bool pending_relax = false;
     int g_sweep = 0;               // persistent grid of k_sweep = rows of `partials`
     std::vector<hipEvent_t> evpool;
-    int g_sweep_key = -1;              // which k_sweep instantiation g_sweep was sized for
+    NkSweepKind g_sweep_kind = {};     // which k_sweep instantiation g_sweep was sized for (g_sweep == 0: none yet)
     size_t g_sweep_lds = 0;            //   and with how much LDS per workgroup
     int layout_key = -1;               // how the particle store was laid out: 1 modes partitioned | 2 ids tracked
     std::vector<double> h_enter_prob;  // host copy of enter_prob (sizes the segments' head room)
@@ -102,7 +104,6 @@ struct nk_ctx {
     int32_t *m2s_dev = nullptr, *s2m_dev = nullptr, *nl_dev = nullptr;
     unsigned int *rbar = nullptr;     // k_resident: step word, halt word, one flag per workgroup
     bool walked = false;              // box store: sweeps have alternated since the segments were last moved down (NkDev::seg_lo may be > 0)
-    int64_t ev_lds_set = -1;          // dynamic LDS k_events was last allowed (hipFuncSetAttribute)
     int map_nseg = 0;                 // segmentation the map was dealt for
     NkMode *modetab_p = nullptr;      // permuted mode table (own allocation: its size follows nseg)
     int64_t modetab_p_len = 0;
@@ -248,6 +249,8 @@ static inline size_t nk_lds(const nk_ctx *ctx, bool geom, int kind = 0) {
     const int gm = geom ? nk_geom_mode(ctx) : 0;
     return nk_lds_bytes(d.S, d.R, d.F, d.NP, d.Fc, gm, kind, (gm == 1 && d.res_lds) ? d.res_nf : 0, d.rbf_P, d.nlrec, nk_want_split(ctx) ? 0 : 1);
 }
+// k_tail: the emission's tables or the reduce's scratch, whichever is larger
+static inline size_t nk_tail_lds(const nk_ctx *ctx) { return std::max(nk_lds(ctx, true, 1), (size_t)(NK_WG * 8 + 16)); }
 #define NK_GEOM_LAUNCH(kernel, grid, lds, ...)                                                        \
     do {                                                                                               \
         if (nk_geom_mode(ctx) == 1) kernel<1><<<grid, NK_WG, lds, ctx->stream>>>(__VA_ARGS__);         \
@@ -261,36 +264,6 @@ static inline size_t nk_lds(const nk_ctx *ctx, bool geom, int kind = 0) {
         else kernel<2, false><<<grid, NK_WG, lds, ctx->stream>>>(__VA_ARGS__);                         \
     } while (0)
 static inline int nk_sweep_grid(const nk_ctx *ctx) { return ctx->num_cu * 8; }
-// The sweep is instantiated per (table placement, rough facets, RBF temperatures, particle ids, split): run STMT with
-// KERNEL bound to the one that matches.  Rough facets draw random numbers per particle, so they imply ids.  The last
-// parameter says where the mode records are read from (LDS copies of the segment's share, or the table in HBM).
-#define NK_SWEEP_CASE(G, R, B, P, S, lrec, STMT) { if (lrec) { auto KERNEL = k_sweep<G, R, B, P, S, true>; STMT; } else { auto KERNEL = k_sweep<G, R, B, P, S, false>; STMT; } }
-// the plain sweep of small meshes also exists with the commonest switches compiled in (nk_sweep_fast)
-#define NK_SWEEP_CASE_FAST(lrec, fast, STMT)                                                                                   \
-    { if (lrec) { if ((fast) == 1) { auto KERNEL = k_sweep<1, false, false, false, false, true, 1>; STMT; } else { auto KERNEL = k_sweep<1, false, false, false, false, true, 2>; STMT; } } \
-      else { if ((fast) == 1) { auto KERNEL = k_sweep<1, false, false, false, false, false, 1>; STMT; } else { auto KERNEL = k_sweep<1, false, false, false, false, false, 2>; STMT; } } }
-#define NK_SWEEP_CASE_S(G, R, B, P, split, lrec, STMT) { if (split) NK_SWEEP_CASE(G, R, B, P, true, lrec, STMT) else NK_SWEEP_CASE(G, R, B, P, false, lrec, STMT) }
-#define NK_SWEEP_CASE_RP(G, B, rough, pid, split, lrec, STMT)                                         \
-    { if (rough) NK_SWEEP_CASE_S(G, true, B, true, split, lrec, STMT) else if (pid) NK_SWEEP_CASE_S(G, false, B, true, split, lrec, STMT) else NK_SWEEP_CASE_S(G, false, B, false, split, lrec, STMT) }
-// ... and every sweep of a small mesh exists for the box store (k_sweep's BOX; ctx->d.box decides)
-#define NK_SWEEP_CASE_BOX(R, B, P, lrec, STMT) { if (lrec) { auto KERNEL = k_sweep<1, R, B, P, false, true, 0, true>; STMT; } else { auto KERNEL = k_sweep<1, R, B, P, false, false, 0, true>; STMT; } }
-#define NK_SWEEP_CASE_BOX_RP(B, rough, pid, lrec, STMT)                                               \
-    { if (rough) NK_SWEEP_CASE_BOX(true, B, true, lrec, STMT) else if (pid) NK_SWEEP_CASE_BOX(false, B, true, lrec, STMT) else NK_SWEEP_CASE_BOX(false, B, false, lrec, STMT) }
-#define NK_SWEEP_CASE_FAST_BOX(lrec, fast, STMT)                                                                               \
-    { if (lrec) { if ((fast) == 1) { auto KERNEL = k_sweep<1, false, false, false, false, true, 1, true>; STMT; } else { auto KERNEL = k_sweep<1, false, false, false, false, true, 2, true>; STMT; } } \
-      else { if ((fast) == 1) { auto KERNEL = k_sweep<1, false, false, false, false, false, 1, true>; STMT; } else { auto KERNEL = k_sweep<1, false, false, false, false, false, 2, true>; STMT; } } }
-#define NK_SWEEP_DISPATCH(gm, rough, rbf, pid, split, lrec, STMT)                                     \
-    do {                                                                                               \
-        const int fast_ = ((gm) == 1 && !(rough) && !(rbf) && !(pid) && !(split)) ? nk_sweep_fast(ctx) : 0;   \
-        if (ctx->d.box && (gm) == 1 && !(split)) {                                                     \
-            if (fast_) { NK_SWEEP_CASE_FAST_BOX(lrec, fast_, STMT) break; }                            \
-            if (rbf) NK_SWEEP_CASE_BOX_RP(true, rough, pid, lrec, STMT) else NK_SWEEP_CASE_BOX_RP(false, rough, pid, lrec, STMT)   \
-            break;                                                                                     \
-        }                                                                                              \
-        if (fast_) { NK_SWEEP_CASE_FAST(lrec, fast_, STMT) break; }                                    \
-        if ((gm) == 1) { if (rbf) NK_SWEEP_CASE_RP(1, true, rough, pid, split, lrec, STMT) else NK_SWEEP_CASE_RP(1, false, rough, pid, split, lrec, STMT) }   \
-        else { if (rbf) NK_SWEEP_CASE_RP(2, true, rough, pid, split, lrec, STMT) else NK_SWEEP_CASE_RP(2, false, rough, pid, split, lrec, STMT) }             \
-    } while (0)
 // 1 / 2: slice subvolumes, 'nearest' / 'linear' particle temperatures and the local reference temperature (k_sweep's FAST)
 static inline int nk_sweep_fast(const nk_ctx *ctx) {
     const NkDev &d = ctx->d;
@@ -299,15 +272,20 @@ static inline int nk_sweep_fast(const nk_ctx *ctx) {
 }
 // the sweep keeps its segments' mode records in LDS when the modes are partitioned over the segments and a segment's share fits
 static inline bool nk_want_lrec(const nk_ctx *ctx) { return ctx->d.nlrec > 0; }      // decided with the segmentation (nk_alloc_particles)
-// k_events, the same way
-#define NK_EVENTS_CASE(G, R, B, P, STMT) { auto KERNEL = k_events<G, R, B, P>; STMT; }
-#define NK_EVENTS_CASE_RP(G, B, rough, pid, STMT)                                                     \
-    { if (rough) NK_EVENTS_CASE(G, true, B, true, STMT) else if (pid) NK_EVENTS_CASE(G, false, B, true, STMT) else NK_EVENTS_CASE(G, false, B, false, STMT) }
-#define NK_EVENTS_DISPATCH(gm, rough, rbf, pid, STMT)                                                 \
-    do {                                                                                               \
-        if ((gm) == 1) { if (rbf) NK_EVENTS_CASE_RP(1, true, rough, pid, STMT) else NK_EVENTS_CASE_RP(1, false, rough, pid, STMT) }   \
-        else { if (rbf) NK_EVENTS_CASE_RP(2, true, rough, pid, STMT) else NK_EVENTS_CASE_RP(2, false, rough, pid, STMT) }             \
-    } while (0)
+
+// nk_kind.h: the dynamic LDS every kernel function has been allowed so far, per device, for the whole process
+hipError_t nk_allow_lds(const void *fn, size_t bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> allowed;
+    int device = 0;
+    if (bytes <= 64 * 1024) return hipSuccess;
+    hipError_t e = hipGetDevice(&device);
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &mark = allowed[{device, fn}];
+    if (e != hipSuccess || bytes <= mark) return e;
+    if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) == hipSuccess) mark = bytes;
+    return e;
+}
 
 // The mode records hold three lifetime rows (two grid intervals) around the live temperature range [T_lo, T_hi] and
 // E0 = exp(hbar omega / (kB T0)) at its middle T0 (nk_device.h "lean FP64 arithmetic"); rebuilt when the range leaves the
@@ -1303,26 +1281,55 @@ static inline bool nk_want_split(const nk_ctx *ctx) {
 }
 static inline bool nk_want_part(const nk_ctx *ctx) { return !getenv("NK_NO_PARTITION"); }   // env: developer probe
 
+// The instantiation this context runs (nk_kind.h), derived here and nowhere else.  Ids and the split sweep are read from the store
+// as it is laid out (stored: d.pid, d.qx) or from what the configuration asks for (nk_want_pid, nk_want_split): nk_sweep_blocks
+// runs inside nk_alloc_particles, before the store exists, and asks for the wanted ones; the steps launch on the store they have.
+// nk_check_ready re-deals a store whose layout_key (written by nk_alloc_particles from d.pid and d.qx) differs from the wanted
+// one, so after it the two readings agree.  The box store has one source: nk_alloc_particles sets d.box = nk_want_box before it
+// sizes the grid, and layout_key covers it too.
+static NkSweepKind nk_sweep_kind(const nk_ctx *ctx, bool stored) {
+    const NkDev &d = ctx->d;
+    return nk_kind_normalise({nk_geom_mode(ctx), d.Fr > 0, d.sv_interp == 3, stored ? (bool)d.pid : nk_want_pid(ctx),
+                              stored ? d.qx != nullptr : nk_want_split(ctx), nk_want_lrec(ctx), nk_sweep_fast(ctx), d.box != 0});
+}
+// One picker per kernel family: the instantiation of a (normalised) kind as a pointer, nullptr for a combination that does not
+// exist (`if constexpr`: it is never named, so never instantiated).  The FAST sweeps are instantiated in nk_sweep_plain.hip.
+typedef void (*NkSweepFn)(NkDev, uint32_t, int, int);
+typedef void (*NkResidentFn)(NkDev, uint32_t, int, int, int, double *, int, unsigned int *);
+static NkSweepFn nk_sweep_kernel(const NkSweepKind &k) {
+    auto fast = [](auto L, auto F1, auto X) -> NkSweepFn { return k_sweep<1, false, false, false, false, L.value, F1.value ? 1 : 2, X.value>; };
+    if (k.fast) return nk_lift(fast, k.lrec, k.fast == 1, k.box);
+    return nk_lift([](auto G1, auto R, auto B, auto P, auto S, auto L, auto X) -> NkSweepFn {
+        if constexpr ((R.value && !P.value) || (X.value && (!G1.value || S.value))) return nullptr;
+        else return k_sweep<G1.value ? 1 : 2, R.value, B.value, P.value, S.value, L.value, 0, X.value>;
+    }, k.geom == 1, k.rough, k.rbf, k.pid, k.split, k.lrec, k.box);
+}
+static NkSweepFn nk_events_kernel(const NkSweepKind &k) {
+    return nk_lift([](auto G1, auto R, auto B, auto P) -> NkSweepFn {
+        if constexpr (R.value && !P.value) return nullptr;
+        else return k_events<G1.value ? 1 : 2, R.value, B.value, P.value>;
+    }, k.geom == 1, k.rough, k.rbf, k.pid);
+}
+static NkResidentFn nk_resident_kernel(const NkSweepKind &k) {
+    return nk_lift([](auto X, auto P, auto L) -> NkResidentFn { return k_resident<X.value, P.value, L.value>; }, k.box, k.pid, k.lrec);
+}
+
 // Persistent grid of the sweep = what the device keeps resident of the instantiation this configuration uses (before the
 // tables are known: four workgroups per CU, the common case).
 static int nk_sweep_blocks(nk_ctx *ctx) {
-    NkDev &d = ctx->d;
     if (!(ctx->have_material && ctx->have_mesh && ctx->have_sv)) return ctx->num_cu * NK_SWEEP_OCC;
-    const int gm_ = nk_geom_mode(ctx);
-    const bool rough_ = d.Fr > 0, rbf_ = d.sv_interp == 3, pid_ = nk_want_pid(ctx), split_ = nk_want_split(ctx);
-    const bool lrec_ = nk_want_lrec(ctx);
-    const int key = gm_ | (rough_ << 2) | (rbf_ << 3) | (pid_ << 4) | (split_ << 5) | (lrec_ << 6) | (nk_sweep_fast(ctx) << 7) | ((d.box ? 1 : 0) << 9);
-    const size_t lds_w = nk_lds(ctx, true, pid_ ? 3 : 2);
-    if (ctx->g_sweep == 0 || ctx->g_sweep_key != key || ctx->g_sweep_lds != lds_w) {
+    const NkSweepKind kind = nk_sweep_kind(ctx, false);
+    const size_t lds_w = nk_lds(ctx, true, kind.pid ? 3 : 2);
+    if (ctx->g_sweep == 0 || !(ctx->g_sweep_kind == kind) || ctx->g_sweep_lds != lds_w) {
         int per_cu = 0;
-        hipError_t e_ = hipSuccess;
-        NK_SWEEP_DISPATCH(gm_, rough_, rbf_, pid_, split_, lrec_, (e_ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, NK_WG, lds_w)));
+        const NkSweepFn sweep = nk_sweep_kernel(kind);          // (nullptr: one workgroup per CU here, the step reports it)
+        hipError_t e_ = sweep ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweep, NK_WG, lds_w) : hipErrorInvalidDeviceFunction;
         if (e_ != hipSuccess || per_cu < 1) per_cu = 1;
         if (per_cu > 8) per_cu = 8;
-        { const int bound = NK_SWEEP_BOUND(gm_, rough_, rbf_, split_); if (per_cu > bound) per_cu = bound; }   // what it was compiled for
+        { const int bound = NK_SWEEP_BOUND(kind.geom, kind.rough, kind.rbf, kind.split); if (per_cu > bound) per_cu = bound; }   // what it was compiled for
         if (const char *e = getenv("NK_SWEEP_PER_CU")) { int v = atoi(e); if (v >= 1 && v < per_cu) per_cu = v; }   // developer probe
         ctx->g_sweep = ctx->num_cu * per_cu;
-        ctx->g_sweep_key = key;
+        ctx->g_sweep_kind = kind;
         ctx->g_sweep_lds = lds_w;
         if (getenv("NK_VERBOSE")) fprintf(stderr, "[nanokappa_hip] sweep: %d workgroups per CU (occupancy query rc %d), %zu B LDS each\n", per_cu, (int)e_, lds_w);
     }
@@ -2278,6 +2285,16 @@ static int nk_batch_timing(nk_ctx *ctx, int nev, int32_t nsteps, int32_t nd) {
 #ifdef NK_STAMPS
 #include "nk_stamps.h"
 #endif
+// The one wait of a stepping call (nk_step_batch, nk_group_batch).  A call of a few steps (a driver that steps one by one) is over
+// in a fraction of a millisecond: poll instead of sleeping on the stream -- the wake-up of a blocked wait is a tenth of such a call.
+static int nk_wait_call(hipStream_t stream, int32_t nsteps, std::string &err) {
+    hipError_t e = hipSuccess;
+    const char *what = "hipStreamQuery";
+    if (nsteps <= 4) while ((e = hipStreamQuery(stream)) == hipErrorNotReady) { }
+    if (e == hipSuccess) { what = "hipStreamSynchronize(stream)"; e = hipStreamSynchronize(stream); }
+    if (e != hipSuccess) { err = std::string(what) + ": " + hipGetErrorString(e); return NK_ERR_HIP; }
+    return NK_OK;
+}
 
 // The launch-per-step path: the sequence of a step, written once.
 static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
@@ -2285,14 +2302,14 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     const int R = d.R, NB = d.NB;
     NkBatch b;
     NK_TRY(nk_batch_enter(ctx, nsteps, b));
-    const size_t lds_g = nk_lds(ctx, true), lds_w = nk_lds(ctx, true, d.pid ? 3 : 2), lds_e = nk_lds(ctx, true, 1);
-    const size_t lds_t = lds_e > (size_t)(NK_WG * 8 + 16) ? lds_e : (size_t)(NK_WG * 8 + 16);
+    const size_t lds_g = nk_lds(ctx, true), lds_w = nk_lds(ctx, true, d.pid ? 3 : 2), lds_e = nk_lds(ctx, true, 1), lds_t = nk_tail_lds(ctx);
     const size_t lds_ev = nk_events_lds(ctx, lds_g);
-    const int gm_ = nk_geom_mode(ctx);
-    const bool rough_ = d.Fr > 0, rbf_ = d.sv_interp == 3, pid_ = (bool)d.pid, split_ = d.qx != nullptr;
-    const bool lrec_ = nk_want_lrec(ctx);
+    const NkSweepKind kind = nk_sweep_kind(ctx, true);
+    const NkSweepFn sweep = nk_sweep_kernel(kind), events = kind.split ? nk_events_kernel(kind) : nullptr;
+    NK_ARG(sweep && (events || !kind.split), "nk_step: no k_sweep / k_events is built for this configuration");
+    if (kind.split) NK_HIP(nk_allow_lds((const void *)events, lds_ev));      // (the tree's top levels can take k_events past 64 KB)
     const int g_sweep = b.g_sweep, g_emit = b.g_emit;
-    const int g_ev = split_ ? ctx->num_cu * NK_EV_PER_CU : 0;    // k_events: resident waves drawing from all queues
+    const int g_ev = kind.split ? ctx->num_cu * NK_EV_PER_CU : 0;    // k_events: resident waves drawing from all queues
     const int rows = g_sweep + g_ev;
     // per-kernel timing on the first 4 steps of a batch; none for the short calls of a driver that steps one by one (six event
     // records are a tenth of such a call).  Every record is a marker packet between two dependent kernels: measured ~2 us each
@@ -2318,18 +2335,11 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
         if (s < nev) NK_HIP(hipEventRecord(ev[4 * s + 1], ctx->stream));
         if (b.alt) ctx->walked = true;
         d.down = rec.down;
-        NK_SWEEP_DISPATCH(gm_, rough_, rbf_, pid_, split_, lrec_, (KERNEL<<<g_sweep, NK_WG, lds_w, ctx->stream>>>(d, step, rec.do_relax, do_flux)));
+        sweep<<<g_sweep, NK_WG, lds_w, ctx->stream>>>(d, step, rec.do_relax, do_flux);
         d.down = 0;
-        if (split_) {
+        if (kind.split) {
             k_events_begin<<<1, 1024, 0, ctx->stream>>>(d);
-            const int64_t ev_key = (int64_t)lds_ev * 64 + (gm_ | (rough_ << 2) | (rbf_ << 3) | (pid_ << 4));
-            if (ctx->ev_lds_set != ev_key) {        // more than the default 64 KB of dynamic LDS has to be asked for, per kernel
-                hipError_t ea_ = hipSuccess;
-                NK_EVENTS_DISPATCH(gm_, rough_, rbf_, pid_, (ea_ = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ev)));
-                NK_HIP(ea_);
-                ctx->ev_lds_set = ev_key;
-            }
-            NK_EVENTS_DISPATCH(gm_, rough_, rbf_, pid_, (KERNEL<<<g_ev, NK_EV_WG, lds_ev, ctx->stream>>>(d, step, do_flux, g_sweep)));
+            events<<<g_ev, NK_EV_WG, lds_ev, ctx->stream>>>(d, step, do_flux, g_sweep);
             k_events_end<<<(d.nseg + 255) / 256, 256, 0, ctx->stream>>>(d);
         }
         // rough facets: the migrants of this step go to their segments before the tallies are reduced (and before the next step's
@@ -2358,10 +2368,7 @@ static int nk_step_batch(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, in
     NK_HIP(hipGetLastError());
     // the history rows and the halt words come back through pinned memory, enqueued behind the steps: ONE wait per call (a
     // Population.run_timestep is one such call per step -- the reference driver's granularity, nanokappa.py:91-98)
-    // a call of a few steps (a driver that steps one by one) is over in a fraction of a millisecond: poll instead of sleeping on the
-    // stream -- the wake-up of a blocked wait is a tenth of such a call
-    if (nsteps <= 4) { hipError_t q_; while ((q_ = hipStreamQuery(ctx->stream)) == hipErrorNotReady) { } if (q_ != hipSuccess) { ctx->err = std::string("hipStreamQuery: ") + hipGetErrorString(q_); return NK_ERR_HIP; } }
-    NK_HIP(hipStreamSynchronize(ctx->stream));
+    NK_TRY(nk_wait_call(ctx->stream, nsteps, ctx->err));
     NK_TRY(nk_batch_collect(ctx, nsteps, h, done));
 #ifdef NK_STAMPS
     NK_TRY(nk_stamps_report(ctx));
@@ -2386,34 +2393,23 @@ static inline bool nk_want_resident(const nk_ctx *ctx) {
     const int64_t lim = getenv("NK_RESIDENT_MAX") ? atoll(getenv("NK_RESIDENT_MAX")) : 1200000;
     return d.cap <= lim && nk_lds(ctx, true, 5) <= 160 * 1024;
 }
-#define NK_RESIDENT_CASE(B, P, lrec, STMT) { if (lrec) { auto KERNEL = k_resident<B, P, true>; STMT; } else { auto KERNEL = k_resident<B, P, false>; STMT; } }
-#define NK_RESIDENT_DISPATCH(box, pid, lrec, STMT)                                                    \
-    do {                                                                                               \
-        if (box) { if (pid) NK_RESIDENT_CASE(true, true, lrec, STMT) else NK_RESIDENT_CASE(true, false, lrec, STMT) }   \
-        else { if (pid) NK_RESIDENT_CASE(false, true, lrec, STMT) else NK_RESIDENT_CASE(false, false, lrec, STMT) }      \
-    } while (0)
 // The resident path: one launch for every run of steps up to the next contains-check step.
 static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h, int32_t *done) {
     NkDev &d = ctx->d;
     const int NB = d.NB;
     NkBatch b;
     NK_TRY(nk_batch_enter(ctx, nsteps, b, true));     // (moves the segments down: the preludes then launch no k_anchor)
-    const bool pid_ = (bool)d.pid, lrec_ = nk_want_lrec(ctx), box_ = d.box != 0;
-    const size_t lds = nk_lds(ctx, true, pid_ ? 5 : 4);
+    const NkSweepKind kind = nk_sweep_kind(ctx, true);            // (nk_want_resident: tables in LDS, no split -- kind.box is d.box)
+    const NkResidentFn resident = nk_resident_kernel(kind);
+    NK_ARG(resident, "nk_step: no k_resident is built for this configuration");
+    const size_t lds = nk_lds(ctx, true, kind.pid ? 5 : 4);
+    // more dynamic LDS than the default limit of a launch has to be allowed (if that fails, the launch itself will say it does not fit)
+    if (nk_allow_lds((const void *)resident, lds) != hipSuccess) (void)hipGetLastError();
     // every workgroup must be resident for the grid barrier: no more than the device holds at once (occupancy query), and no
     // more than there are segments
-    if (lds > 64 * 1024) {                                        // more dynamic LDS than the default limit of a launch
-        hipError_t ea = hipSuccess;
-        NK_RESIDENT_DISPATCH(box_, pid_, lrec_, (ea = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
-        if (ea != hipSuccess) (void)hipGetLastError();            // (the launch itself will say if it does not fit)
-    }
     int per_cu = 1;
-    {
-        hipError_t eo = hipSuccess;
-        NK_RESIDENT_DISPATCH(box_, pid_, lrec_, (eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, NK_WG, lds)));
-        if (eo != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-        if (per_cu > 2) per_cu = 2;
-    }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident, NK_WG, lds) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    if (per_cu > 2) per_cu = 2;
     int G = std::min(ctx->num_cu * per_cu, (d.nseg + NK_WG / 64 - 1) / (NK_WG / 64));
     if (const char *e = getenv("NK_RESIDENT_GRID")) { const int v = atoi(e); if (v >= 1 && v < G) G = v; }   // developer probe
     G = std::max(1, G);
@@ -2429,8 +2425,7 @@ static int nk_step_resident(nk_ctx *ctx, int32_t nsteps, std::vector<double> &h,
         int n = 1;                                                // the steps of this launch: up to the next contains-check step
         while (k + n < nsteps && !nk_contains_step(ctx, ctx->step + k + n)) ++n;
         NK_HIP(hipMemsetAsync(ctx->rbar, 0, (32 + 1024 + 128) * sizeof(unsigned int), ctx->stream));     // the flags count from 1 in every launch
-        NK_RESIDENT_DISPATCH(box_, pid_, lrec_, (KERNEL<<<G, NK_WG, lds, ctx->stream>>>(d, rec.step, n, rec.do_relax, ctx->params.flux_every,
-                                                                                       rec.hist_row, nk_row(ctx).width(), ctx->rbar)));
+        resident<<<G, NK_WG, lds, ctx->stream>>>(d, rec.step, n, rec.do_relax, ctx->params.flux_every, rec.hist_row, nk_row(ctx).width(), ctx->rbar);
         NK_HIP(hipGetLastError());
         k += n;
     }
@@ -2643,7 +2638,7 @@ static thread_local std::string g_group_error;
 
 // what the shared launches bake in: the members of a group agree on all of it
 struct NkGroupKey {
-    NkGroupKind kind;
+    NkSweepKind kind;
     int S, R, NB, flux_every, contains_every, res_gen;
     double dt;
     int64_t step;
@@ -2651,10 +2646,7 @@ struct NkGroupKey {
 static NkGroupKey nk_group_key(nk_ctx *ctx) {
     const NkDev &d = ctx->d;
     NkGroupKey k;
-    k.kind.pid = (bool)d.pid;
-    k.kind.lrec = nk_want_lrec(ctx);
-    k.kind.fast = k.kind.pid ? 0 : nk_sweep_fast(ctx);
-    k.kind.box = d.box != 0;
+    k.kind = nk_sweep_kind(ctx, true);                  // (the store's: nk_group_check has run nk_check_ready on every member)
     k.S = d.S; k.R = d.R; k.NB = d.NB;
     k.flux_every = ctx->params.flux_every; k.contains_every = ctx->params.contains_every; k.res_gen = d.res_gen;
     k.dt = d.dt;
@@ -2706,8 +2698,7 @@ static int nk_group_check(nk_ctx *const *m, int R, NkGroupPlan *plan, std::strin
     }
     size_t lds_w = 0, lds_t = 0;
     for (int r = 0; r < R; ++r) {
-        const size_t w = nk_lds(m[r], true, m[r]->d.pid ? 3 : 2), e = nk_lds(m[r], true, 1);
-        const size_t tl = e > (size_t)(NK_WG * 8 + 16) ? e : (size_t)(NK_WG * 8 + 16);          // (k_tail: the emission's tables or the reduce's scratch)
+        const size_t w = nk_lds(m[r], true, m[r]->d.pid ? 3 : 2), tl = nk_tail_lds(m[r]);
         if (w > 64 * 1024 || tl > 64 * 1024) { err = "nk_group: member " + std::to_string(r) + " is outside the grouped path: its tables need more than 64 KB of LDS"; return NK_ERR_ARG; }
         lds_w = std::max(lds_w, w); lds_t = std::max(lds_t, tl);
     }
@@ -2729,6 +2720,11 @@ static int nk_group_check(nk_ctx *const *m, int R, NkGroupPlan *plan, std::strin
         NK_GROUP_SAME(kind.lrec, "kernel instantiation (mode records in LDS)")
         NK_GROUP_SAME(kind.fast, "kernel instantiation (subvolume fast path)")
         NK_GROUP_SAME(kind.box, "kernel instantiation (box store)")
+        // (nk_group_scope admits one value of each of these: a disagreement would be a fault of the scope's)
+        NK_GROUP_SAME(kind.geom, "kernel instantiation (table placement)")
+        NK_GROUP_SAME(kind.rough, "kernel instantiation (rough facets)")
+        NK_GROUP_SAME(kind.rbf, "kernel instantiation (RBF temperatures)")
+        NK_GROUP_SAME(kind.split, "kernel instantiation (split sweep)")
 #undef NK_GROUP_SAME
         if (what) {
             err = "nk_group: member " + std::to_string(r) + " disagrees with member 0 on the " + what + " (" + a + " against " + b + ")";
@@ -2867,9 +2863,7 @@ static int nk_group_batch(nk_group *g, const NkGroupPlan &plan, hipStream_t stre
     NK_GHIP(hipGetLastError());
     g->rep.grid_sweep = grid_sweep;
     g->rep.grid_tail = grid_tail;
-    // ONE wait per call; a call of a few steps polls instead of sleeping on the stream (nk_step_batch)
-    if (nsteps <= 4) { hipError_t q_; while ((q_ = hipStreamQuery(stream)) == hipErrorNotReady) { } if (q_ != hipSuccess) { g->err = std::string("hipStreamQuery: ") + hipGetErrorString(q_); return NK_ERR_HIP; } }
-    NK_GHIP(hipStreamSynchronize(stream));
+    if ((rc = nk_wait_call(stream, nsteps, g->err))) return rc;      // ONE wait per call
     bool all_ran = true;
     for (int r = 0; r < R; ++r) {
         nk_ctx *ctx = g->m[r];

@@ -22,7 +22,6 @@ struct NkFieldGrid {
     long long *status = nullptr;          // [nstatus] samples, clamped, overflow E, overflow F (field: 4) [, ungrouped, -, -, - (groups: 8)]
     int32_t nstatus = 0;
     int64_t bytes = 0;                    // device memory of this grid (the groups': with their tables)
-    int lds_attr[2] = {0, 0};             // dynamic LDS the step / state instantiation of k_field that fills THIS grid was last allowed
 };
 
 struct NkFieldHost {

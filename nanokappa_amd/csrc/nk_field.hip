@@ -13,8 +13,9 @@
 #define NK_KERNEL_LINKAGE template <int NK_NOT_IN_THIS_TU = 0>
 #include "nk_kernels.h"
 #include "nk_field.h"
+#include "nk_kind.h"
 
-// LDS a launch may ask for on gfx950 (160 KB per CU; above 64 KB hipFuncSetAttribute has to allow it per kernel)
+// LDS a launch may ask for on gfx950 (160 KB per CU; above 64 KB nk_allow_lds has to allow it per kernel)
 static const size_t NK_FIELD_LDS_MAX = 160 * 1024;
 // bins of one line in LDS: E, Fx, Fy, Fz (u64) + N (u32)
 static const size_t NK_FIELD_LDS_LINE = 36;
@@ -356,13 +357,9 @@ bool nk_field_lds_bins(const NkFieldGrid &g, bool force_global, size_t lds0, siz
 }
 
 template <bool STATE, bool GROUPED>
-static hipError_t nk_field_launch(int *lds_attr, int nwg, size_t lds, const NkDev &d, const NkFieldDev &f, hipStream_t stream) {
-    // (one entry per kernel FUNCTION: an entry shared by two instantiations would skip an attribute one of them needs)
-    if (lds > 65536 && *lds_attr < (int)lds) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_field<STATE, GROUPED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        *lds_attr = (int)lds;
-    }
+static hipError_t nk_field_launch(int nwg, size_t lds, const NkDev &d, const NkFieldDev &f, hipStream_t stream) {
+    hipError_t e = nk_allow_lds((const void *)k_field<STATE, GROUPED>, lds);
+    if (e != hipSuccess) return e;
     k_field<STATE, GROUPED><<<nwg, NK_FIELD_WG, lds, stream>>>(d, f);
     return hipGetLastError();
 }
@@ -390,9 +387,8 @@ hipError_t nk_field_pass(NkFieldHost &F, NkFGroupsHost *Gh, const NkDev &d, bool
     // two 1024-thread workgroups per CU where their LDS allows it, else one
     const int per_cu = 2 * lds <= NK_FIELD_LDS_MAX ? 2 : 1;
     const int nwg = std::max(1, std::min(per_cu * num_cu, (int)d.nseg));
-    int *attr = &g.lds_attr[state ? 1 : 0];
-    if (Gh) return state ? nk_field_launch<true, true>(attr, nwg, lds, d, f, stream) : nk_field_launch<false, true>(attr, nwg, lds, d, f, stream);
-    return state ? nk_field_launch<true, false>(attr, nwg, lds, d, f, stream) : nk_field_launch<false, false>(attr, nwg, lds, d, f, stream);
+    if (Gh) return state ? nk_field_launch<true, true>(nwg, lds, d, f, stream) : nk_field_launch<false, true>(nwg, lds, d, f, stream);
+    return state ? nk_field_launch<true, false>(nwg, lds, d, f, stream) : nk_field_launch<false, false>(nwg, lds, d, f, stream);
 }
 
 hipError_t nk_field_accumulate(NkFieldGrid &g, const NkFieldHost &F, int nranks, hipStream_t stream) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nk_kind.h"
 
 struct NkDev;
 
@@ -27,12 +28,10 @@ struct NkGroupRec {
     double *hist_row, *acc;
 };
 
-// which k_sweep the group's sweep mirrors: particle ids, mode records in LDS, FAST 0 / 1 / 2, box store
-struct NkGroupKind { bool pid, lrec; int fast; bool box; };
-
-hipError_t nk_group_launch_sweep(const NkGroupKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
+// k: the kind of the k_sweep that the group's sweep mirrors (nk_kind.h; a group's scope leaves pid, lrec, fast and box open)
+hipError_t nk_group_launch_sweep(const NkSweepKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
                                  const NkGroupRec *recs);
 // the FAST instantiations live in an object of their own, built with the flags of nk_sweep_plain.hip (Makefile)
-hipError_t nk_group_launch_sweep_fast(const NkGroupKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
+hipError_t nk_group_launch_sweep_fast(const NkSweepKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
                                       const NkGroupRec *recs);
 hipError_t nk_group_launch_tail(bool box, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs, const NkGroupRec *recs);

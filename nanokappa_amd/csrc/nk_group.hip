@@ -54,19 +54,16 @@ __global__ __launch_bounds__(NK_WG, NK_SWEEP_BOUND(1, false, false, false)) void
     nk_lds_flush(d, L, wg);
 }
 
+typedef void (*NkGroupSweepFn)(const NkGroupHead *, const NkDev *, const NkGroupRec *);
+
 #ifdef NK_GROUP_PLAIN
 
-#define NK_GROUP_SWEEP(P, L, F, B) k_sweep_group<P, L, F, B><<<grid, NK_WG, lds, stream>>>(head, devs, recs)
-hipError_t nk_group_launch_sweep_fast(const NkGroupKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
+hipError_t nk_group_launch_sweep_fast(const NkSweepKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
                                       const NkGroupRec *recs) {
     if (k.pid || (k.fast != 1 && k.fast != 2)) return hipErrorInvalidValue;
-    if (k.box) {
-        if (k.lrec) { if (k.fast == 1) NK_GROUP_SWEEP(false, true, 1, true); else NK_GROUP_SWEEP(false, true, 2, true); }
-        else { if (k.fast == 1) NK_GROUP_SWEEP(false, false, 1, true); else NK_GROUP_SWEEP(false, false, 2, true); }
-    } else {
-        if (k.lrec) { if (k.fast == 1) NK_GROUP_SWEEP(false, true, 1, false); else NK_GROUP_SWEEP(false, true, 2, false); }
-        else { if (k.fast == 1) NK_GROUP_SWEEP(false, false, 1, false); else NK_GROUP_SWEEP(false, false, 2, false); }
-    }
+    const NkGroupSweepFn fn = nk_lift([](auto L, auto F1, auto X) -> NkGroupSweepFn { return k_sweep_group<false, L.value, F1.value ? 1 : 2, X.value>; },
+                                      k.lrec, k.fast == 1, k.box);
+    fn<<<grid, NK_WG, lds, stream>>>(head, devs, recs);
     return hipGetLastError();
 }
 
@@ -94,17 +91,12 @@ __global__ __launch_bounds__(NK_WG) void k_tail_group(const NkGroupHead *head_, 
     }
 }
 
-#define NK_GROUP_SWEEP(P, L, B) k_sweep_group<P, L, 0, B><<<grid, NK_WG, lds, stream>>>(head, devs, recs)
-hipError_t nk_group_launch_sweep(const NkGroupKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
+hipError_t nk_group_launch_sweep(const NkSweepKind &k, int grid, size_t lds, hipStream_t stream, const NkGroupHead *head, const NkDev *devs,
                                  const NkGroupRec *recs) {
     if (k.fast) return nk_group_launch_sweep_fast(k, grid, lds, stream, head, devs, recs);
-    if (k.box) {
-        if (k.pid) { if (k.lrec) NK_GROUP_SWEEP(true, true, true); else NK_GROUP_SWEEP(true, false, true); }
-        else { if (k.lrec) NK_GROUP_SWEEP(false, true, true); else NK_GROUP_SWEEP(false, false, true); }
-    } else {
-        if (k.pid) { if (k.lrec) NK_GROUP_SWEEP(true, true, false); else NK_GROUP_SWEEP(true, false, false); }
-        else { if (k.lrec) NK_GROUP_SWEEP(false, true, false); else NK_GROUP_SWEEP(false, false, false); }
-    }
+    const NkGroupSweepFn fn = nk_lift([](auto P, auto L, auto X) -> NkGroupSweepFn { return k_sweep_group<P.value, L.value, 0, X.value>; },
+                                      k.pid, k.lrec, k.box);
+    fn<<<grid, NK_WG, lds, stream>>>(head, devs, recs);
     return hipGetLastError();
 }
 

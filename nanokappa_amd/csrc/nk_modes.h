@@ -22,7 +22,6 @@ struct NkModesHost {
     double *accE = nullptr, *accN = nullptr;   // [nbins] sums over the samples since the last reset (this rank's particles)
     long long *status = nullptr;          // [4] samples, skipped, overflow E, -
     int64_t bytes = 0;
-    int lds_attr[2] = {0, 0};             // dynamic LDS the two instantiations of k_modes were last allowed
 };
 
 void nk_modes_free(NkModesHost &Mo);

@@ -13,8 +13,9 @@
 #include "nk_kernels.h"
 #include "nk_field.h"
 #include "nk_modes.h"
+#include "nk_kind.h"
 
-// LDS a launch may ask for on gfx950 (160 KB per CU; above 64 KB hipFuncSetAttribute has to allow it per kernel)
+// LDS a launch may ask for on gfx950 (160 KB per CU; above 64 KB nk_allow_lds has to allow it per kernel)
 static const size_t NK_MODES_LDS_MAX = 160 * 1024;
 // bins of one (mode, subvolume) in LDS: E (u64) + N (u32)
 static const size_t NK_MODES_LDS_BIN = 12;
@@ -126,11 +127,8 @@ hipError_t nk_modes_pass(NkModesHost &Mo, const NkDev &d, bool state, size_t lds
     // two 1024-thread workgroups per CU (the threads a CU holds), fewer where there are fewer groups of segments
     const int G = std::max(1, std::min(2 * num_cu, ((int)d.nseg + nteam - 1) / nteam));
     const void *fn = state ? (const void *)k_modes<true> : (const void *)k_modes<false>;
-    if (lds > 65536 && Mo.lds_attr[state ? 1 : 0] < (int)lds) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        Mo.lds_attr[state ? 1 : 0] = (int)lds;
-    }
+    hipError_t e = nk_allow_lds(fn, lds);
+    if (e != hipSuccess) return e;
     if (state) k_modes<true><<<G, NK_MODES_WG, lds, stream>>>(d, m);
     else k_modes<false><<<G, NK_MODES_WG, lds, stream>>>(d, m);
     return hipGetLastError();

@@ -71,7 +71,7 @@ def scan(lines, start, stop, pending):
     return bad, pending, first_wait, last_load
 
 
-# Every SPLIT instantiation NK_SWEEP_DISPATCH can reach (nk_engine.hip): tables in global memory (GEOM 2: the default reason for
+# Every SPLIT instantiation nk_sweep_kernel can return (nk_engine.hip; the kinds of nk_kind.h): tables in global memory (GEOM 2: the default reason for
 # a split sweep) and, forced with NK_SPLIT=1, in LDS (GEOM 1); rough facets imply ids; RBF temperatures or not; mode records from
 # LDS or from the table.  <GEOM, ROUGH, RBF, PID, SPLIT, LREC, FAST>
 SPLIT_INSTANCES = ['%d, %s, %s, %s, true, %s, 0' % (g, r, b, p, l)
