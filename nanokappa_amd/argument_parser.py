@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep` and `--free_path_map`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep`, `--free_path_map` and `--kinetic`."""
 import argparse
 import os
 import sys
@@ -75,6 +75,12 @@ def initialise_parser(debug_flag=False):
            'velocity until a boundary ends them, weighed with the lifetimes at T (default: the mean reservoir temperature) -- '
            'and write k_free_path.txt (tensor with its standard error, bulk value, accumulation over the mean free path) and '
            'free_path.npz (per-mode arrays); off by default')
+    a('--kinetic', default=[], type=str, nargs='*',
+      help='N [T] [max_events]: before the first step, solve the steady linearised BTE (relaxation time) by kinetic flights on the '
+           'GPU -- N energy packets from every reservoir (T facet), flown, scattered with the lifetimes at T (default: the mean '
+           'reservoir temperature), re-emitted by diffuse walls and absorbed by reservoirs -- and write k_kinetic.txt (conductance '
+           'between the reservoirs with its standard error, kappa_eff between two parallel reservoirs, the bulk value) and '
+           'kinetic.npz (transmission, temperature deviation and heat flux per subvolume); off by default')
     a('--free_path_sweep', default=[], type=str, nargs='*',
       help='scale s1 s2 ... | temperature T1 T2 ...: with --free_path N, also weigh the same rays once per value (at most 32) -- '
            'the structure scaled by s with unchanged roughness, or the structure as it is at the temperature T (K) -- and write '

@@ -26,6 +26,7 @@
 #include "nk_group.h"
 #include "nk_freepath.h"
 #include "nk_freecols.h"
+#include "nk_kinetic.h"
 // instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
 #ifndef NK_PLAIN_IN_ENGINE
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
@@ -149,6 +150,7 @@ struct nk_ctx {
     // free-path sampling (nk_free_paths, k_free_paths<*, false>; nk_freepath.hip): the last call's report -- nothing is kept on the device
     nk_free_path_report fp_last = {};
     int32_t fc_calls = 0;        // nk_free_paths_columns calls so far (k_free_columns; nk_freecols.hip)
+    int32_t kin_calls = 0;       // nk_kinetic_flights calls so far (k_kinetic; nk_kinetic.hip)
     nk_free_path_map_report fm_last = {};   // the last nk_free_paths_map call's report (k_free_paths<*, true>; nk_freepath.hip)
 };
 
@@ -4213,5 +4215,143 @@ int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_pat
 int nk_free_paths_map_info(nk_ctx *ctx, nk_free_path_map_report *out) {
     NK_ARG(ctx && out, "nk_free_paths_map_info: NULL argument");
     *out = ctx->fm_last;
+    return NK_OK;
+}
+
+// ------------------------------------------------------------------------------------- kinetic flights
+// k_kinetic (nk_kinetic.hip) on buffers of this call alone: the particle store, its counters, the step counter and the emission
+// bookkeeping are neither read nor written.
+static int nk_kin_table(nk_ctx *ctx, const char *name, const double *t, int64_t M) {
+    NK_ARG(t, std::string("nk_kinetic_flights: ") + name + " is NULL (a cumulative table over all Q*J modes)");
+    double prev = 0.0;
+    for (int64_t m = 0; m < M; ++m) {
+        NK_ARG(t[m] >= prev && t[m] <= 1.0, std::string("nk_kinetic_flights: ") + name + " is not a cumulative table (entry " + std::to_string((long long)m) + ")");
+        prev = t[m];
+    }
+    NK_ARG(M > 0 && t[M - 1] == 1.0, std::string("nk_kinetic_flights: ") + name + " does not end at 1 (no live mode?)");
+    return NK_OK;
+}
+int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_out *out, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
+    if (rep) memset(rep, 0, sizeof(*rep));
+    NK_ARG(ctx && a, "nk_kinetic_flights: NULL argument");
+    NK_ARG(ctx->have_material, "nk_kinetic_flights: no material (nk_set_material first)");
+    NK_ARG(ctx->have_mesh, "nk_kinetic_flights: no mesh (nk_set_mesh first)");
+    NK_ARG(ctx->have_sv, "nk_kinetic_flights: no subvolumes (nk_set_subvolumes first)");
+    const NkDev &d = ctx->d;
+    const int64_t M = d.M;
+    NK_ARG(ctx->h_vg.size() == (size_t)M * 3, "nk_kinetic_flights: no group velocities (nk_set_material first)");
+    NK_ARG(a->n_samples > 0, "nk_kinetic_flights: n_samples = " + std::to_string(a->n_samples) + " must be positive");
+    NK_ARG(a->max_events >= 0 && a->max_events <= (1 << 30), "nk_kinetic_flights: max_events must be 0 .. 2^30");
+    NK_ARG(a->rays_per_wave >= 0, "nk_kinetic_flights: rays_per_wave must not be negative");
+    NK_ARG(a->tau, "nk_kinetic_flights: tau is NULL (the lifetimes of all Q*J modes)");
+    nk_kinetic_report r;
+    memset(&r, 0, sizeof(r));
+    NkKinDev f;
+    memset(&f, 0, sizeof(f));
+    for (int fc = 0; fc < d.Fc; ++fc) {
+        const NkFacet &q = ctx->host_facets[fc];
+        NK_ARG(q.bc != 'F', "nk_kinetic_flights: facet " + std::to_string(fc) + " has boundary condition 'F' (a fixed heat flux): the kinetic flights take reservoirs 'T', periodic 'P' and rough 'R' facets only");
+        if (q.bc == 'T') {
+            NK_ARG(r.n_sources < NK_KIN_MAX_SOURCES, "nk_kinetic_flights: more than " + std::to_string(NK_KIN_MAX_SOURCES) + " facets with boundary condition 'T' (the sources)");
+            NK_ARG(ctx->h_ffo[fc + 1] > ctx->h_ffo[fc], "nk_kinetic_flights: source facet " + std::to_string(fc) + " has no faces");
+            f.src_facet[r.n_sources] = fc; r.source_facet[r.n_sources] = fc;
+            ++r.n_sources;
+        }
+    }
+    NK_ARG(r.n_sources > 0, "nk_kinetic_flights: no facet with boundary condition 'T': nothing emits");
+    for (int fc = 0; fc < d.Fc; ++fc) {
+        const NkFacet &q = ctx->host_facets[fc];
+        NK_ARG(q.bc != 'R' || (q.rough >= 0 && q.rough < d.Fr && d.specularity),
+               "nk_kinetic_flights: facet " + std::to_string(fc) + " is rough ('R') but no rough tables are installed (nk_set_rough or nk_rough_finish)");
+    }
+    NK_TRY(nk_kin_table(ctx, "cdf_scatter", a->cdf_scatter, M));
+    NK_TRY(nk_kin_table(ctx, "cdf_flux", a->cdf_flux, M));
+    const int64_t n = a->n_samples, rays = n * r.n_sources;
+    NK_ARG(rays < (1ll << 31), "nk_kinetic_flights: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    // bounds and scales: a segment lasts min(t_s, t_c), t_s <= 38 tau (u >= 2^-54) and, cast from inside the mesh, t_c <= 2 diagonal / |v|
+    double diag = 0.0;
+    for (int c = 0; c < 3; ++c) diag += (d.bbox[3 + c] - d.bbox[c]) * (d.bbox[3 + c] - d.bbox[c]);
+    diag = sqrt(diag);
+    double Bt = 0.0, Bx = 0.0;
+    for (int64_t m = 0; m < M; ++m) {
+        const bool live = a->cdf_scatter[m] > (m ? a->cdf_scatter[m - 1] : 0.0);
+        if (!live) continue;
+        const double t = a->tau[m];
+        NK_ARG(t > 0.0 && !std::isnan(t), "nk_kinetic_flights: mode " + std::to_string((long long)m) + " is drawn by cdf_scatter but its tau is not positive");
+        const double *v = &ctx->h_vg[3 * (size_t)m];
+        const double sp = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        const double tb = sp > 0.0 ? std::min(38.0 * t, 2.0 * diag / sp) : 38.0 * t;
+        NK_ARG(std::isfinite(tb), "nk_kinetic_flights: mode " + std::to_string((long long)m) + " does not move and never scatters (tau is not finite)");
+        Bt = std::max(Bt, tb);
+        Bx = std::max(Bx, tb * std::max(std::max(fabs(v[0]), fabs(v[1])), fabs(v[2])));
+    }
+    NK_ARG(Bt > 0.0, "nk_kinetic_flights: no live mode");
+    Bx = std::max(Bx, 1e-300);
+    f.nsrc = r.n_sources; f.n = a->n_samples;
+    f.max_events = a->max_events > 0 ? a->max_events : (1 << 20);
+    f.rays_per_wave = a->rays_per_wave > 0 ? a->rays_per_wave : 512;
+    f.blocks = (int32_t)((n + f.rays_per_wave - 1) / f.rays_per_wave);
+    f.M = (int32_t)M;
+    f.seed = a->seed ? a->seed : d.seed;
+    r.B_t = Bt; r.B_x = Bx;
+    f.Bt = Bt; f.Bx = Bx; f.BT = 1024.0 * Bt; f.BD = 1024.0 * Bx; f.BD2 = (32.0 * Bx) * (32.0 * Bx);
+    const int64_t cap_seg = n * (int64_t)f.max_events;          // (< 2^61)
+    r.k_t = nk_field_k(f.Bt, cap_seg); r.k_x = nk_field_k(f.Bx, cap_seg);
+    r.k_T = nk_field_k(f.BT, n); r.k_D = nk_field_k(f.BD, n); r.k_D2 = nk_field_k(f.BD2, n);
+    f.st = ldexp(1.0, r.k_t); f.sx = ldexp(1.0, r.k_x); f.sT = ldexp(1.0, r.k_T); f.sD = ldexp(1.0, r.k_D); f.sD2 = ldexp(1.0, r.k_D2);
+    r.rays = rays; r.n_subvolumes = d.S;
+    r.geometry_mode = nk_geom_mode(ctx);
+    const size_t lds0 = (nk_lds(ctx, true) + 15) & ~(size_t)15;
+    const int64_t nsub = (int64_t)r.n_sources * d.S * 4;
+    r.lds_bins = (!a->no_bins && lds0 + (size_t)nsub * 8 <= 64 * 1024) ? 1 : 0;
+    f.bins_off = (int32_t)lds0;
+    const size_t lds = r.lds_bins ? lds0 + (size_t)nsub * 8 : nk_lds(ctx, true);
+    r.grid = (f.nsrc * f.blocks + NK_KIN_WAVES - 1) / NK_KIN_WAVES;
+    r.calls = ctx->kin_calls + 1;
+    NK_HIP(hipSetDevice(ctx->device));
+    const bool w = pr != nullptr;
+    NK_BUF(double, dtau, a->tau, M); NK_BUF(double, dcs, a->cdf_scatter, M); NK_BUF(double, dcf, a->cdf_flux, M);
+    NK_BUF(unsigned long long, drows, nullptr, (int64_t)r.n_sources * NK_KIN_ROW); NK_BUF(unsigned long long, dsub, nullptr, nsub);
+    NK_BUF(double, rx, nullptr, (w && pr->x0) ? rays * 3 : 0); NK_BUF(double, rD, nullptr, (w && pr->D) ? rays * 3 : 0);
+    NK_BUF(double, rT, nullptr, (w && pr->dwell) ? rays : 0);
+    NK_BUF(int32_t, rm, nullptr, (w && pr->mode) ? rays : 0); NK_BUF(int32_t, re, nullptr, (w && pr->end) ? rays : 0);
+    NK_BUF(int32_t, rv, nullptr, (w && pr->events) ? rays : 0); NK_BUF(int32_t, rc, nullptr, (w && pr->casts) ? rays : 0);
+    NK_BUF(unsigned long long, rh, nullptr, (w && pr->hash) ? rays : 0);
+    f.tau = dtau.p; f.vg = ctx->d_vg; f.cdf_scatter = dcs.p; f.cdf_flux = dcf.p;
+    f.rows = drows.p; f.sub = dsub.p;
+    f.ray_x0 = (w && pr->x0) ? rx.p : nullptr; f.ray_D = (w && pr->D) ? rD.p : nullptr; f.ray_T = (w && pr->dwell) ? rT.p : nullptr;
+    f.ray_mode = (w && pr->mode) ? rm.p : nullptr; f.ray_end = (w && pr->end) ? re.p : nullptr;
+    f.ray_events = (w && pr->events) ? rv.p : nullptr; f.ray_casts = (w && pr->casts) ? rc.p : nullptr;
+    f.ray_hash = (w && pr->hash) ? rh.p : nullptr;
+    r.bytes = M * 24 + ((int64_t)r.n_sources * NK_KIN_ROW + nsub) * 8 + (f.ray_x0 ? rays * 24 : 0) + (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) +
+              (f.ray_mode ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0) + (f.ray_events ? rays * 4 : 0) + (f.ray_casts ? rays * 4 : 0) + (f.ray_hash ? rays * 8 : 0);
+    NK_HIP(hipMemsetAsync(drows.p, 0, (size_t)r.n_sources * NK_KIN_ROW * 8, ctx->stream));      // (outside the timed window)
+    NK_HIP(hipMemsetAsync(dsub.p, 0, (size_t)std::max<int64_t>(nsub, 1) * 8, ctx->stream));
+    NK_HIP(nk_free_timed(ctx->stream, r.seconds, [&] { return nk_kinetic_launch(d, f, r.geometry_mode, lds, r.lds_bins != 0, ctx->stream); }));
+    std::vector<unsigned long long> hrows((size_t)r.n_sources * NK_KIN_ROW);
+    NK_HIP(drows.get(hrows.data(), (int64_t)hrows.size()));
+    int64_t ov[5] = {0, 0, 0, 0, 0};
+    for (int s = 0; s < r.n_sources; ++s) {
+        const unsigned long long *q = &hrows[(size_t)s * NK_KIN_ROW];
+        r.lost += (int64_t)q[NK_KR_LOST]; r.missed += (int64_t)q[NK_KR_MISSED]; r.capped += (int64_t)q[NK_KR_CAPPED];
+        r.events += (int64_t)q[NK_KR_EVENTS]; r.casts += (int64_t)q[NK_KR_CASTS];
+        for (int j = 0; j < 5; ++j) ov[j] += (int64_t)q[NK_KR_OVD + j];
+    }
+    r.overflow = ov[0] + ov[1] + ov[2] + ov[3] + ov[4];
+    if (out && out->rows) memcpy(out->rows, hrows.data(), hrows.size() * 8);
+    if (out && out->sub) NK_HIP(hipMemcpy(out->sub, dsub.p, (size_t)nsub * 8, hipMemcpyDeviceToHost));
+    if (w) {
+        NK_HIP(rx.get(pr->x0, rays * 3)); NK_HIP(rD.get(pr->D, rays * 3)); NK_HIP(rT.get(pr->dwell, rays));
+        NK_HIP(rm.get(pr->mode, rays)); NK_HIP(re.get(pr->end, rays)); NK_HIP(rv.get(pr->events, rays)); NK_HIP(rc.get(pr->casts, rays));
+        NK_HIP(rh.get((unsigned long long *)pr->hash, rays));
+    }
+    ctx->kin_calls = r.calls;
+    if (rep) *rep = r;
+    if (r.overflow) {
+        ctx->err = "nk_kinetic_flights: overflow: " + std::to_string((long long)ov[0]) + " displacement(s), " + std::to_string((long long)ov[1]) +
+                   " squared displacement(s) and " + std::to_string((long long)ov[2]) + " dwell time(s) of a ray, " + std::to_string((long long)ov[3]) +
+                   " time(s) and " + std::to_string((long long)ov[4]) + " displacement(s) of a segment above their bounds; they were left out of the sums";
+        return NK_ERR_CAPACITY;
+    }
     return NK_OK;
 }

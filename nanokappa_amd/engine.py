@@ -93,7 +93,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
            'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info', 'nk_free_paths_columns',
-           'nk_free_paths_map', 'nk_free_paths_map_info']
+           'nk_free_paths_map', 'nk_free_paths_map_info', 'nk_kinetic_flights']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -174,6 +174,33 @@ class nk_free_path_map_report(C.Structure):
                 ('seconds', C.c_double)]
 
 
+KIN_MAX_SOURCES = 8          # NK_KIN_MAX_SOURCES (include/nanokappa_hip.h)
+KIN_ROW_WORDS = 32           # NK_KIN_ROW_WORDS
+
+
+class nk_kinetic_args(C.Structure):
+    _fields_ = [('n_samples', C.c_int32), ('max_events', C.c_int32), ('rays_per_wave', C.c_int32), ('no_bins', C.c_int32),
+                ('tau', c_dp), ('cdf_scatter', c_dp), ('cdf_flux', c_dp), ('seed', C.c_uint64)]
+
+
+class nk_kinetic_out(C.Structure):
+    _fields_ = [('rows', C.POINTER(C.c_int64)), ('sub', C.POINTER(C.c_int64))]
+
+
+class nk_kinetic_rays(C.Structure):
+    _fields_ = [('x0', c_dp), ('mode', c_ip), ('end', c_ip), ('events', c_ip), ('casts', c_ip), ('D', c_dp), ('dwell', c_dp),
+                ('hash', c_u64p)]
+
+
+class nk_kinetic_report(C.Structure):
+    _fields_ = [('rays', C.c_int64), ('events', C.c_int64), ('casts', C.c_int64), ('lost', C.c_int64), ('missed', C.c_int64),
+                ('capped', C.c_int64), ('overflow', C.c_int64), ('n_sources', C.c_int32), ('n_subvolumes', C.c_int32),
+                ('source_facet', C.c_int32 * KIN_MAX_SOURCES), ('k_D', C.c_int32), ('k_D2', C.c_int32), ('k_T', C.c_int32),
+                ('k_t', C.c_int32), ('k_x', C.c_int32), ('geometry_mode', C.c_int32), ('lds_bins', C.c_int32), ('grid', C.c_int32),
+                ('calls', C.c_int32), ('pad_', C.c_int32), ('B_t', C.c_double), ('B_x', C.c_double), ('bytes', C.c_int64),
+                ('seconds', C.c_double)]
+
+
 class nk_group_report(C.Structure):
     _fields_ = [('R', C.c_int32), ('halted', C.c_int32), ('finished_alone', C.c_int32), ('grid_sweep', C.c_int32),
                 ('grid_tail', C.c_int32), ('pad_', C.c_int32), ('steps', C.c_int64), ('sweep_launches', C.c_int64),
@@ -182,6 +209,7 @@ class nk_group_report(C.Structure):
 
 
 ERR_ARG = -2                 # NK_ERR_ARG (include/nanokappa_hip.h)
+ERR_CAPACITY = -3            # NK_ERR_CAPACITY
 GROUP_MAX_MEMBERS = 32       # NK_GROUP_MAX_MEMBERS
 MODES_GLOBAL = 1             # nk_set_modes flags (include/nanokappa_hip.h)
 MODES_TEST_SMALL_BOUND = 2
@@ -281,6 +309,8 @@ def load_library():
     L.nk_free_paths_map_info.argtypes = [C.c_void_p, C.POINTER(nk_free_path_map_report)]
     L.nk_free_paths_columns.argtypes = [C.c_void_p, C.POINTER(nk_free_path_args), C.c_int32, C.POINTER(nk_free_path_modes),
                                         C.POINTER(nk_free_path_rays), C.POINTER(nk_free_path_columns_report)]
+    L.nk_kinetic_flights.argtypes = [C.c_void_p, C.POINTER(nk_kinetic_args), C.POINTER(nk_kinetic_out), C.POINTER(nk_kinetic_rays),
+                                     C.POINTER(nk_kinetic_report)]
     _lib = L
     return L
 
@@ -887,6 +917,62 @@ class Engine(object):
         rep = nk_free_path_map_report()
         self._ck(self.L.nk_free_paths_map_info(self.h, C.byref(rep)), 'nk_free_paths_map_info')
         return self._free_path_map_report(rep)
+
+    # ------------------------------------------------------- kinetic flights
+    def kinetic_flights(self, tau, c, n=65536, max_events=0, seed=0, rays=False, rays_per_wave=0, lds_bins=True):
+        """Kinetic flights (nk_kinetic_flights; k_kinetic): n energy packets from every 'T' facet, flown, scattered (tau [Q*J], drawn
+        in proportion to c / tau, c [Q*J] the volumetric heat capacity per mode), re-emitted by diffuse walls and absorbed by the
+        reservoirs -- the steady linearised BTE in the relaxation-time picture (kinetic.py forms conductances and profiles).
+        max_events 0 = 2^20, seed 0 = the engine's; rays_per_wave (0 = 512) sets the launch grid and lds_bins=False sends the
+        per-subvolume words straight to memory: neither changes a bit of the result.  Returns a dict: n, source_facet [F], ends
+        [F, F] (rays from f absorbed at g), lost, missed, capped, events, casts [F], the sums over a source's rays D, D2 [F, 3] and
+        dwell_total [F], per subvolume dwell [F, S] and flux [F, S, 3] (the sum of t v), the raw integers rows [F, 32] and sub
+        [F, S, 4] with the report's scales k_*, cdf_scatter, cdf_flux, report; with rays=True also ray_x0 [F, n, 3], ray_mode,
+        ray_end (>= 0 the absorbing source, -1 lost, -2 missed, -3 capped), ray_events, ray_casts, ray_D [F, n, 3], ray_dwell and
+        ray_hash [F, n].  Touches neither the particles nor the step counter."""
+        from . import kinetic as KN
+        n = int(n)
+        t, cc = _d(np.ravel(tau)), _d(np.ravel(c))
+        if self.M > 0 and (t.shape[0] != self.M or cc.shape[0] != self.M):
+            raise NkError('kinetic_flights: tau has %d and c %d entries, the material %d modes' % (t.shape[0], cc.shape[0], self.M))
+        try:
+            cs, cf = KN.tables(cc, t, self._vg)
+        except ValueError as e:
+            raise NkError('kinetic_flights: %s' % e)
+        cs, cf = _d(cs), _d(cf)
+        a = nk_kinetic_args()
+        a.n_samples, a.max_events, a.rays_per_wave, a.no_bins = n, int(max_events), int(rays_per_wave), 0 if lds_bins else 1
+        a.tau, a.cdf_scatter, a.cdf_flux, a.seed = _p(t), _p(cs), _p(cf), int(seed)
+        F, S, nn = KIN_MAX_SOURCES, max(self.S, 1), max(n, 0)
+        rows, sub = np.zeros((F, KIN_ROW_WORDS), dtype=np.int64), np.zeros(F * S * 4, dtype=np.int64)
+        o = nk_kinetic_out()
+        o.rows, o.sub = rows.ctypes.data_as(C.POINTER(C.c_int64)), sub.ctypes.data_as(C.POINTER(C.c_int64))
+        pr, ro = None, {}
+        if rays:
+            ro = dict(ray_x0=np.zeros((F, nn, 3)), ray_mode=np.zeros((F, nn), dtype=np.int32), ray_end=np.zeros((F, nn), dtype=np.int32),
+                      ray_events=np.zeros((F, nn), dtype=np.int32), ray_casts=np.zeros((F, nn), dtype=np.int32), ray_D=np.zeros((F, nn, 3)),
+                      ray_dwell=np.zeros((F, nn)), ray_hash=np.zeros((F, nn), dtype=np.uint64))
+            pr = nk_kinetic_rays()
+            pr.x0, pr.D, pr.dwell = _p(ro['ray_x0']), _p(ro['ray_D']), _p(ro['ray_dwell'])
+            pr.mode, pr.end, pr.events, pr.casts = (_p(ro[k], c_ip) for k in ('ray_mode', 'ray_end', 'ray_events', 'ray_casts'))
+            pr.hash = _p(ro['ray_hash'], c_u64p)
+        rep = nk_kinetic_report()
+        rc = self.L.nk_kinetic_flights(self.h, C.byref(a), C.byref(o), C.byref(pr) if pr else None, C.byref(rep))
+        r = {k: (list(getattr(rep, k)) if k == 'source_facet' else getattr(rep, k)) for k, _ in nk_kinetic_report._fields_ if k != 'pad_'}
+        if rc != 0 and not (rc == ERR_CAPACITY and r['overflow'] > 0):
+            self._ck(rc, 'nk_kinetic_flights')
+        nf = int(rep.n_sources)
+        r['source_facet'] = r['source_facet'][:nf]
+        r['message'] = self.L.nk_last_error(self.h).decode() if rc != 0 else ''
+        rows, sub = rows[:nf].copy(), sub[:nf * S * 4].reshape(nf, S, 4).copy()
+        out = dict(n=n, source_facet=np.array(r['source_facet'], dtype=np.int32), ends=rows[:, :nf].copy(), lost=rows[:, 8].copy(),
+                   missed=rows[:, 9].copy(), capped=rows[:, 10].copy(), events=rows[:, 11].copy(), casts=rows[:, 12].copy(),
+                   D=rows[:, 13:16] * 2.0 ** -r['k_D'], D2=rows[:, 16:19] * 2.0 ** -r['k_D2'], dwell_total=rows[:, 19] * 2.0 ** -r['k_T'],
+                   dwell=sub[:, :, 0] * 2.0 ** -r['k_t'], flux=sub[:, :, 1:4] * 2.0 ** -r['k_x'], rows=rows, sub=sub,
+                   cdf_scatter=cs, cdf_flux=cf, report=r)
+        for k, v in ro.items():
+            out[k] = v[:nf].copy()
+        return out
 
     def get_step(self):
         """Timesteps this engine has completed (the library's absolute step counter: flux and contains_check cadence)."""

@@ -27,6 +27,7 @@ from . import modes as MD
 from . import free_path as FP
 from . import free_sweep as FS
 from . import free_map as FM
+from . import kinetic as KN
 from .engine import Engine
 from .sharding import shard_range
 
@@ -566,6 +567,33 @@ class Population(Constants):
         if write and self.results_folder_name:
             FP.write_k_free_path(FP.k_free_path_path(self.results_folder_name), s)
             FP.write_free_path_npz(FP.free_path_npz_path(self.results_folder_name), s)
+        return s
+
+    def kinetic_flights(self, n=KN.N_DEFAULT, T=None, tau=None, max_events=KN.MAX_EVENTS_DEFAULT, seed=0, write=True):
+        """Conductance between the reservoirs and the temperature and heat-flux profile of the steady linearised BTE, by kinetic
+        flights on the GPU (Engine.kinetic_flights): n energy packets from every 'T' facet with the lifetimes `tau` [Q*J]
+        (default: Phonon.lifetime_function at T, itself by default the mean reservoir temperature) and the heat capacities at T.
+        Returns kinetic.summarise()'s dict (G [F, F] in W/K with its standard error, per subvolume dT and q for the geometry's
+        reservoir temperatures, kappa_eff between two parallel reservoirs with the bulk value and the free-path closed form
+        beside it) and, with a results folder, writes k_kinetic.txt and kinetic.npz.  May be called at any point of a run:
+        particles and step counter are not touched.  With several ranks rank 0 computes and writes; the others return None."""
+        if self.rank != 0:
+            return None
+        ph, geo = self._ph, self._geo
+        T = self._mean_reservoir_T() if T is None else float(T)
+        tau = FP.lifetimes(ph, T) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
+        qv = ph.number_of_qpoints * ph.volume_unitcell
+        c = KN.heat_capacity(ph.omega, T, qv, self.hbar, self.kb)
+        src = KN.source_facets(geo.bound_cond)
+        res = self.engine.kinetic_flights(tau, c, n=int(n), max_events=int(max_events), seed=int(seed))
+        T_f = np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src])
+        pair = KN.parallel_pair(src, geo.facets_normal, geo.facets_area, geo.facet_centroid)
+        s = KN.summarise(res, c, ph.group_vel, tau, T, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,
+                         geo.subvol_volume, pair=pair, omega_c=FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb), qv=qv)
+        self.kinetic_last = s
+        if write and self.results_folder_name:
+            KN.write_k_kinetic(KN.k_kinetic_path(self.results_folder_name), s)
+            KN.write_kinetic_npz(KN.kinetic_npz_path(self.results_folder_name), s)
         return s
 
     def free_path_sweep(self, kind, values, n=FP.N_DEFAULT, T=None, modes=None, max_segments=FP.MAX_SEGMENTS_DEFAULT, w_min=FP.W_MIN_DEFAULT,
