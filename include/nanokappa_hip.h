@@ -602,6 +602,32 @@ typedef struct {
 int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *args, const nk_kinetic_out *out, const nk_kinetic_rays *rays,
                        nk_kinetic_report *report);
 
+/* Kinetic groups: nk_kinetic_flights with the per-subvolume words also split by group of modes -- which phonons carry the heat.
+ * The table names the group 0 .. n_groups-1 of every mode, or -1; a segment's four words {t, t v_x, t v_y, t v_z} (the same
+ * quantised integers as `sub`) go to the column of the mode the segment was FLOWN in (the mode before the event that ends it
+ * changes it).  There are n_groups + 1 columns: the last one, the REST column, takes every mode whose entry is -1 (a live mode
+ * that does not move has no mean free path and no direction), so the columns of a (source, subvolume) always add up to its words
+ * in `sub` -- as integers, bit for bit: the kernel tallies the columns only and `sub` is folded from them by integer adds
+ * (k_kinetic_fold), which gives the bits of an ungrouped call.  Everything else -- rows, the per-ray outputs, the report -- is what
+ * nk_kinetic_flights returns for the same arguments; both entries run through one host function.  The columns are gathered in
+ * LDS bins where n_sources * S * (n_groups + 1) * 4 words fit behind the mesh tables in 64 KB and go straight to memory otherwise
+ * (the report's lds_bins says which; the same bits). */
+#define NK_KIN_MAX_GROUPS 256
+#define NK_KIN_MAX_GROUP_WORDS (1 << 24)
+typedef struct {
+    int32_t n_groups;            /* 1 .. NK_KIN_MAX_GROUPS */
+    const int32_t *group_of_mode; /* [Q*J], -1 .. n_groups-1 */
+} nk_kinetic_groups;
+typedef struct {                 /* the pointer may be NULL */
+    int64_t *grp;                /* [n_sources * S * (n_groups + 1) * 4] per (source, subvolume, column): dwell 2^k_t, t v_x, t v_y,
+                                  * t v_z 2^k_x; column n_groups is the rest column */
+} nk_kinetic_group_out;
+/* NK_ERR_ARG as nk_kinetic_flights, and with a text that names the cause: groups or its table NULL; n_groups < 1 or >
+ * NK_KIN_MAX_GROUPS; a table entry outside -1 .. n_groups-1; n_sources * S * (n_groups + 1) * 4 above NK_KIN_MAX_GROUP_WORDS.
+ * Nothing is launched or allocated then. */
+int nk_kinetic_flights_groups(nk_ctx *ctx, const nk_kinetic_args *args, const nk_kinetic_groups *groups, const nk_kinetic_out *out,
+                              const nk_kinetic_group_out *group_out, const nk_kinetic_rays *rays, nk_kinetic_report *report);
+
 /* Replica groups: R contexts that hold the same problem under different seeds (the runs behind an error bar) are stepped by
  * shared launches -- per step ONE sweep and ONE tail launch for all of them instead of R of each, and one wait per call.  A
  * workgroup of the shared launch finds its member and runs that member's step exactly as nk_step would: the rows and the

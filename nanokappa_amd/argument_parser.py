@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep`, `--free_path_map` and `--kinetic`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep`, `--free_path_map`, `--kinetic` and `--kinetic_groups`."""
 import argparse
 import os
 import sys
@@ -81,6 +81,14 @@ def initialise_parser(debug_flag=False):
            'reservoir temperature), re-emitted by diffuse walls and absorbed by reservoirs -- and write k_kinetic.txt (conductance '
            'between the reservoirs with its standard error, kappa_eff between two parallel reservoirs, the bulk value) and '
            'kinetic.npz (transmission, temperature deviation and heat flux per subvolume); off by default')
+    a('--kinetic_groups', default=[], type=str, nargs='*',
+      help='G kind [axis]: with --kinetic N, also tally the flights\' dwell time and heat flux per (subvolume, group of modes) on '
+           'the GPU, in 8 batches of N / 8 rays whose spread gives the error bars, and write k_kinetic_groups.txt (one line per '
+           'group: its edges, its share of the conductivity between the reservoirs with its standard error, the bulk share, their '
+           'ratio, the running sum -- the accumulation function with the contacts included) and kinetic_groups.npz (per group the '
+           'temperature deviation and heat flux of every subvolume); kind = frequency (G bins), branch, mfp (G log-spaced bins of '
+           'the mean free path of the call\'s lifetimes) or direction (G bins of the cosine between the group velocity and the '
+           'axis x|y|z, default the transport axis); off by default')
     a('--free_path_sweep', default=[], type=str, nargs='*',
       help='scale s1 s2 ... | temperature T1 T2 ...: with --free_path N, also weigh the same rays once per value (at most 32) -- '
            'the structure scaled by s with unchanged roughness, or the structure as it is at the temperature T (K) -- and write '

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <queue>
 #include <string>
@@ -4231,9 +4232,12 @@ static int nk_kin_table(nk_ctx *ctx, const char *name, const double *t, int64_t 
     NK_ARG(M > 0 && t[M - 1] == 1.0, std::string("nk_kinetic_flights: ") + name + " does not end at 1 (no live mode?)");
     return NK_OK;
 }
-int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_out *out, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
+// Both entries: nk_kinetic_flights is this function without groups (g and gout null).
+static int nk_kin_run(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_groups *g, const nk_kinetic_out *out,
+                      const nk_kinetic_group_out *gout, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
     if (rep) memset(rep, 0, sizeof(*rep));
-    NK_ARG(ctx && a, "nk_kinetic_flights: NULL argument");
+    if (!ctx) return NK_ERR_ARG;                                // (no context to hold a text)
+    NK_ARG(a, "nk_kinetic_flights: NULL argument");
     NK_ARG(ctx->have_material, "nk_kinetic_flights: no material (nk_set_material first)");
     NK_ARG(ctx->have_mesh, "nk_kinetic_flights: no mesh (nk_set_mesh first)");
     NK_ARG(ctx->have_sv, "nk_kinetic_flights: no subvolumes (nk_set_subvolumes first)");
@@ -4268,6 +4272,22 @@ int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_o
     NK_TRY(nk_kin_table(ctx, "cdf_flux", a->cdf_flux, M));
     const int64_t n = a->n_samples, rays = n * r.n_sources;
     NK_ARG(rays < (1ll << 31), "nk_kinetic_flights: " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    // kinetic groups: n_groups + 1 columns, the last one for the modes whose entry is -1
+    int32_t GC = 0;
+    if (g) {
+        NK_ARG(g->n_groups >= 1 && g->n_groups <= NK_KIN_MAX_GROUPS, "nk_kinetic_flights_groups: n_groups = " + std::to_string(g->n_groups) +
+                                                                         " must be 1 .. " + std::to_string(NK_KIN_MAX_GROUPS));
+        GC = g->n_groups + 1;                                   // (after the range check: no overflow)
+        NK_ARG(g->group_of_mode, "nk_kinetic_flights_groups: group_of_mode is NULL (the group of all Q*J modes, -1 .. n_groups-1)");
+        for (int64_t m = 0; m < M; ++m)
+            NK_ARG(g->group_of_mode[m] >= -1 && g->group_of_mode[m] < g->n_groups,
+                   "nk_kinetic_flights_groups: group_of_mode[" + std::to_string((long long)m) + "] = " + std::to_string(g->group_of_mode[m]) +
+                       " is outside -1 .. " + std::to_string(g->n_groups - 1));
+        const int64_t words = (int64_t)r.n_sources * d.S * GC * 4;
+        NK_ARG(words <= NK_KIN_MAX_GROUP_WORDS, "nk_kinetic_flights_groups: " + std::to_string(r.n_sources) + " sources x " + std::to_string(d.S) +
+                                                    " subvolumes x " + std::to_string(GC) + " columns x 4 = " + std::to_string((long long)words) +
+                                                    " words are more than a call takes (2^24)");
+    }
     // bounds and scales: a segment lasts min(t_s, t_c), t_s <= 38 tau (u >= 2^-54) and, cast from inside the mesh, t_c <= 2 diagonal / |v|
     double diag = 0.0;
     for (int c = 0; c < 3; ++c) diag += (d.bbox[3 + c] - d.bbox[c]) * (d.bbox[3 + c] - d.bbox[c]);
@@ -4303,9 +4323,11 @@ int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_o
     r.geometry_mode = nk_geom_mode(ctx);
     const size_t lds0 = (nk_lds(ctx, true) + 15) & ~(size_t)15;
     const int64_t nsub = (int64_t)r.n_sources * d.S * 4;
-    r.lds_bins = (!a->no_bins && lds0 + (size_t)nsub * 8 <= 64 * 1024) ? 1 : 0;
+    const int64_t ngrp = nsub * GC;                             // the columns' words; with groups the bins hold these
+    const int64_t nbins = g ? ngrp : nsub;
+    r.lds_bins = (!a->no_bins && lds0 + (size_t)nbins * 8 <= 64 * 1024) ? 1 : 0;
     f.bins_off = (int32_t)lds0;
-    const size_t lds = r.lds_bins ? lds0 + (size_t)nsub * 8 : nk_lds(ctx, true);
+    const size_t lds = r.lds_bins ? lds0 + (size_t)nbins * 8 : nk_lds(ctx, true);
     r.grid = (f.nsrc * f.blocks + NK_KIN_WAVES - 1) / NK_KIN_WAVES;
     r.calls = ctx->kin_calls + 1;
     NK_HIP(hipSetDevice(ctx->device));
@@ -4317,6 +4339,15 @@ int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_o
     NK_BUF(int32_t, rm, nullptr, (w && pr->mode) ? rays : 0); NK_BUF(int32_t, re, nullptr, (w && pr->end) ? rays : 0);
     NK_BUF(int32_t, rv, nullptr, (w && pr->events) ? rays : 0); NK_BUF(int32_t, rc, nullptr, (w && pr->casts) ? rays : 0);
     NK_BUF(unsigned long long, rh, nullptr, (w && pr->hash) ? rays : 0);
+    std::unique_ptr<NkDevBuf<int32_t>> dcol;                    // (a call without groups allocates neither)
+    std::unique_ptr<NkDevBuf<unsigned long long>> dgrp;
+    if (g) {
+        std::vector<int32_t> hcol((size_t)M);
+        for (int64_t m = 0; m < M; ++m) hcol[(size_t)m] = g->group_of_mode[m] < 0 ? g->n_groups : g->group_of_mode[m];
+        dcol.reset(new NkDevBuf<int32_t>(hcol.data(), M)); NK_HIP(dcol->err);
+        dgrp.reset(new NkDevBuf<unsigned long long>(nullptr, ngrp)); NK_HIP(dgrp->err);
+        f.group = dcol->p; f.GC = GC; f.grp = dgrp->p;
+    }
     f.tau = dtau.p; f.vg = ctx->d_vg; f.cdf_scatter = dcs.p; f.cdf_flux = dcf.p;
     f.rows = drows.p; f.sub = dsub.p;
     f.ray_x0 = (w && pr->x0) ? rx.p : nullptr; f.ray_D = (w && pr->D) ? rD.p : nullptr; f.ray_T = (w && pr->dwell) ? rT.p : nullptr;
@@ -4324,9 +4355,11 @@ int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_o
     f.ray_events = (w && pr->events) ? rv.p : nullptr; f.ray_casts = (w && pr->casts) ? rc.p : nullptr;
     f.ray_hash = (w && pr->hash) ? rh.p : nullptr;
     r.bytes = M * 24 + ((int64_t)r.n_sources * NK_KIN_ROW + nsub) * 8 + (f.ray_x0 ? rays * 24 : 0) + (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) +
-              (f.ray_mode ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0) + (f.ray_events ? rays * 4 : 0) + (f.ray_casts ? rays * 4 : 0) + (f.ray_hash ? rays * 8 : 0);
+              (f.ray_mode ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0) + (f.ray_events ? rays * 4 : 0) + (f.ray_casts ? rays * 4 : 0) + (f.ray_hash ? rays * 8 : 0) +
+              (g ? M * 4 + ngrp * 8 : 0);
     NK_HIP(hipMemsetAsync(drows.p, 0, (size_t)r.n_sources * NK_KIN_ROW * 8, ctx->stream));      // (outside the timed window)
     NK_HIP(hipMemsetAsync(dsub.p, 0, (size_t)std::max<int64_t>(nsub, 1) * 8, ctx->stream));
+    if (g) NK_HIP(hipMemsetAsync(dgrp->p, 0, (size_t)std::max<int64_t>(ngrp, 1) * 8, ctx->stream));
     NK_HIP(nk_free_timed(ctx->stream, r.seconds, [&] { return nk_kinetic_launch(d, f, r.geometry_mode, lds, r.lds_bins != 0, ctx->stream); }));
     std::vector<unsigned long long> hrows((size_t)r.n_sources * NK_KIN_ROW);
     NK_HIP(drows.get(hrows.data(), (int64_t)hrows.size()));
@@ -4340,6 +4373,7 @@ int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_o
     r.overflow = ov[0] + ov[1] + ov[2] + ov[3] + ov[4];
     if (out && out->rows) memcpy(out->rows, hrows.data(), hrows.size() * 8);
     if (out && out->sub) NK_HIP(hipMemcpy(out->sub, dsub.p, (size_t)nsub * 8, hipMemcpyDeviceToHost));
+    if (g && gout && gout->grp) NK_HIP(hipMemcpy(gout->grp, dgrp->p, (size_t)ngrp * 8, hipMemcpyDeviceToHost));
     if (w) {
         NK_HIP(rx.get(pr->x0, rays * 3)); NK_HIP(rD.get(pr->D, rays * 3)); NK_HIP(rT.get(pr->dwell, rays));
         NK_HIP(rm.get(pr->mode, rays)); NK_HIP(re.get(pr->end, rays)); NK_HIP(rv.get(pr->events, rays)); NK_HIP(rc.get(pr->casts, rays));
@@ -4354,4 +4388,15 @@ int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_o
         return NK_ERR_CAPACITY;
     }
     return NK_OK;
+}
+int nk_kinetic_flights(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_out *out, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
+    return nk_kin_run(ctx, a, nullptr, out, nullptr, pr, rep);
+}
+int nk_kinetic_flights_groups(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_groups *g, const nk_kinetic_out *out,
+                              const nk_kinetic_group_out *gout, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
+    if (ctx && !g) {                                            // (everything else is nk_kin_run's to check)
+        if (rep) memset(rep, 0, sizeof(*rep));
+        NK_ARG(g, "nk_kinetic_flights_groups: groups is NULL (n_groups and the group of every mode)");
+    }
+    return nk_kin_run(ctx, a, g, out, gout, pr, rep);
 }

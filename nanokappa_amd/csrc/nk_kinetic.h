@@ -1,5 +1,6 @@
-// nk_kinetic.h -- kinetic flights (nk_kinetic_flights): what the kernel k_kinetic<GEOM, BINS> (nk_kinetic.hip, a translation unit of
-// its own like nk_freepath.hip) is handed, and its launch.  The C entry point is in nk_engine.hip.
+// nk_kinetic.h -- kinetic flights (nk_kinetic_flights, nk_kinetic_flights_groups): what the kernel k_kinetic<GEOM, BINS, GROUPED>
+// (nk_kinetic.hip, a translation unit of its own like nk_freepath.hip) is handed, and its launch.  The C entry points are in
+// nk_engine.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,9 +45,15 @@ struct NkKinDev {
     double *ray_x0, *ray_D, *ray_T;                       // [rays * 3], [rays * 3], [rays]
     int32_t *ray_mode, *ray_end, *ray_events, *ray_casts; // [rays]
     unsigned long long *ray_hash;                         // [rays]
+    // kinetic groups (GROUPED; GC = 0 and both pointers null otherwise): a segment's four words go to (source, subvolume, column
+    // of the mode it was flown in) and `sub` is folded from the columns afterwards (k_kinetic_fold)
+    const int32_t *group;                                 // [M] the column of every mode, 0 .. GC-1
+    int32_t GC, pad_;                                     // columns: the call's groups and the rest column
+    unsigned long long *grp;                              // [nsrc * S * GC * 4], zeroed by the host
 };
 
 // one wave per (source, block of rays_per_wave rays); geom = 1 (planes in LDS) or 2 (tables in global memory, tree walk); lds = what
 // nk_lds_setup of that geometry mode and kind 0 needs; bins: the per-subvolume words are gathered in LDS (f.bins_off, nsrc * S * 4
-// words behind lds) before they go to memory
+// words behind lds, times GC where f.GC > 0) before they go to memory.  f.GC > 0 picks the GROUPED instantiations and launches
+// k_kinetic_fold behind them on the same stream
 hipError_t nk_kinetic_launch(const NkDev &d, const NkKinDev &f, int geom, size_t lds, bool bins, hipStream_t stream);

@@ -1,11 +1,12 @@
 // nk_kinetic.hip -- kinetic flights: the deviational, time-step-free Monte Carlo of the steady linearised BTE in the relaxation-time
-// picture (nk_kinetic_flights): k_kinetic<GEOM, BINS> and its launch.  The C entry point is in nk_engine.hip.
+// picture (nk_kinetic_flights, nk_kinetic_flights_groups): k_kinetic<GEOM, BINS, GROUPED>, k_kinetic_fold and their launch.  The C
+// entry points are in nk_engine.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "../../include/nanokappa_hip.h"
 // Every non-template kernel of nk_kernels.h becomes a template here that nothing instantiates, so this file's object holds
-// the four instantiations of k_kinetic and nothing else (the trick of nk_modes.hip).
+// the eight instantiations of k_kinetic, k_kinetic_fold and nothing else (the trick of nk_modes.hip).
 #define NK_KERNEL_LINKAGE template <int NK_NOT_IN_THIS_TU = 0>
 #include "nk_kernels.h"
 #include "nk_kinetic.h"
@@ -53,7 +54,10 @@ __device__ __forceinline__ long long nk_kin_q(double term, double s, double B, u
 }
 
 // the flat lane loop of one wave: the rays [blk * rays_per_wave, ..) of source src
-template <int GEOM, bool BINS>
+// GROUPED (kinetic groups): the lane keeps the column of its mode beside tau -- loaded where tau is, when the mode changes -- and a
+// segment's four words go to (source, subvolume, column) instead of (source, subvolume): the loop still does four adds per segment,
+// and `sub` is folded from the columns afterwards (k_kinetic_fold)
+template <int GEOM, bool BINS, bool GROUPED>
 __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, const NkKinDev &f, int wi, int lane, unsigned long long *bins) {
 #pragma clang fp contract(off)
     const int src = wi / f.blocks, blk = wi - src * f.blocks;
@@ -65,7 +69,8 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
     NkFreeDev ff = {};                                       // what nk_fl_facet reads: the seed and the group velocities
     ff.seed = f.seed; ff.vg = f.vg;
     unsigned long long *sub;
-    if constexpr (BINS) sub = bins + (size_t)src * d.S * 4;
+    if constexpr (GROUPED) sub = (BINS ? bins : f.grp) + (size_t)src * d.S * f.GC * 4;
+    else if constexpr (BINS) sub = bins + (size_t)src * d.S * 4;
     else sub = f.sub + (size_t)src * d.S * 4;
     // the wave's sums
     unsigned int ends[NK_KIN_MAX_SOURCES_DEV];
@@ -76,6 +81,7 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
     long long aD[3] = {0ll, 0ll, 0ll}, aD2[3] = {0ll, 0ll, 0ll}, aT = 0ll;
     // the lane's ray
     int flying = 0, smp = 0, mode = 0, k = 0, ncast = 0, end = 0;
+    [[maybe_unused]] int col = 0;                            // GROUPED: f.group[mode]
     uint64_t rid = 0ull, hash = 0ull;
     double x = 0.0, y = 0.0, z = 0.0, vx = 0.0, vy = 0.0, vz = 0.0, tau = 0.0, Dx = 0.0, Dy = 0.0, Dz = 0.0, T = 0.0;
     for (;;) {
@@ -107,7 +113,10 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
             k = 0; ncast = 0; hash = 0ull; Dx = Dy = Dz = T = 0.0; end = 0;
             mode = -1;
             if (!nk_kin_emit(f, rid, 0u, -fp->nx, -fp->ny, -fp->nz, mode)) { end = NK_KIN_LOST; fin = true; }
-            else { vx = f.vg[3 * (int64_t)mode]; vy = f.vg[3 * (int64_t)mode + 1]; vz = f.vg[3 * (int64_t)mode + 2]; tau = f.tau[mode]; }
+            else {
+                vx = f.vg[3 * (int64_t)mode]; vy = f.vg[3 * (int64_t)mode + 1]; vz = f.vg[3 * (int64_t)mode + 2]; tau = f.tau[mode];
+                if constexpr (GROUPED) col = f.group[mode];
+            }
             const int64_t r = (int64_t)src * f.n + smp;
             if (f.ray_x0) { f.ray_x0[3 * r] = x; f.ray_x0[3 * r + 1] = y; f.ray_x0[3 * r + 2] = z; }
             if (f.ray_mode) f.ray_mode[r] = mode;
@@ -134,7 +143,9 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
                 T = T + t;
                 const double ap = up * t;
                 const int s = nk_classify(d, L.tb, __builtin_fma(ap, vx, x), __builtin_fma(ap, vy, y), __builtin_fma(ap, vz, z));
-                unsigned long long *w = sub + 4 * s;        // s < S
+                unsigned long long *w;                      // s < S (and col < GC: the host checks the table)
+                if constexpr (GROUPED) w = sub + 4 * ((size_t)s * f.GC + col);
+                else w = sub + 4 * s;
                 const long long qt = nk_kin_q(t, f.st, f.Bt, ovSt);
                 const long long qx = nk_kin_q(t * vx, f.sx, f.Bx, ovSx), qy = nk_kin_q(t * vy, f.sx, f.Bx, ovSx), qz = nk_kin_q(t * vz, f.sx, f.Bx, ovSx);
                 if (qt) atomicAdd(w, (unsigned long long)qt);
@@ -162,9 +173,13 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
                         if (what != 0) {                    // diffuse: re-emitted from the hit point
                             x = hx; y = hy; z = hz;
                             if (!nk_kin_emit(f, rid, (uint32_t)k, nx, ny, nz, mode)) { end = NK_KIN_LOST; fin = true; }
-                            else { vx = f.vg[3 * (int64_t)mode]; vy = f.vg[3 * (int64_t)mode + 1]; vz = f.vg[3 * (int64_t)mode + 2]; tau = f.tau[mode]; }
+                            else {
+                                vx = f.vg[3 * (int64_t)mode]; vy = f.vg[3 * (int64_t)mode + 1]; vz = f.vg[3 * (int64_t)mode + 2]; tau = f.tau[mode];
+                                if constexpr (GROUPED) col = f.group[mode];
+                            }
                         } else if (turned) {
                             tau = f.tau[mode];
+                            if constexpr (GROUPED) col = f.group[mode];
                             scatter_now = !(tau > 0.0);     // a specular turn into a mode that does not live
                         }
                     }
@@ -176,6 +191,7 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
                     int m = nk_ss_right(f.cdf_scatter, f.M, us);
                     mode = m > f.M - 1 ? f.M - 1 : m;
                     vx = f.vg[3 * (int64_t)mode]; vy = f.vg[3 * (int64_t)mode + 1]; vz = f.vg[3 * (int64_t)mode + 2]; tau = f.tau[mode];
+                    if constexpr (GROUPED) col = f.group[mode];
                 }
                 if (!fin && k >= f.max_events) { end = NK_KIN_CAPPED; fin = true; }
             }
@@ -215,40 +231,65 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
     }
 }
 
-template <int GEOM, bool BINS>
+template <int GEOM, bool BINS, bool GROUPED>
 __global__ __launch_bounds__(NK_WG) void k_kinetic(NkDev d, NkKinDev f) {
     extern __shared__ __align__(16) unsigned char smem[];
     NkLds L;
     nk_lds_setup<GEOM, 0>(d, smem, L);
     unsigned long long *bins = reinterpret_cast<unsigned long long *>(smem + f.bins_off);
-    const int nb = f.nsrc * d.S * 4;
+    const int nb = GROUPED ? f.nsrc * d.S * f.GC * 4 : f.nsrc * d.S * 4;
     if constexpr (BINS) {
         for (int i = (int)threadIdx.x; i < nb; i += NK_WG) bins[i] = 0ull;
         __syncthreads();
     }
     const int lane = (int)(threadIdx.x & 63u);
     const int wi = __builtin_amdgcn_readfirstlane((int)blockIdx.x * NK_KIN_WAVES + (int)(threadIdx.x >> 6));
-    if (wi < f.nsrc * f.blocks) nk_kin_wave<GEOM, BINS>(d, L, f, wi, lane, bins);
+    if (wi < f.nsrc * f.blocks) nk_kin_wave<GEOM, BINS, GROUPED>(d, L, f, wi, lane, bins);
     if constexpr (BINS) {
         __syncthreads();
+        unsigned long long *out = GROUPED ? f.grp : f.sub;
         for (int i = (int)threadIdx.x; i < nb; i += NK_WG) {
             const unsigned long long v = bins[i];
-            if (v) atomicAdd(f.sub + i, v);
+            if (v) atomicAdd(out + i, v);
         }
     }
 }
 
-// the dispatch of NK_GEOM_LAUNCH (nk_engine.hip): the geometry mode and the bins pick the instantiation
+// kinetic groups: the plain words of (source, subvolume) are the integer sums of its columns' words -- one thread per word of
+// `sub`, launched behind k_kinetic<.., true> on the same stream.  Integer adds commute, so `sub` holds the bits an ungrouped call gives.
+__global__ __launch_bounds__(NK_WG) void k_kinetic_fold(NkKinDev f, int S) {
+    const int i = (int)(blockIdx.x * NK_WG + threadIdx.x);            // (source * S + subvolume) * 4 + word
+    if (i >= f.nsrc * S * 4) return;
+    const unsigned long long *g = f.grp + (size_t)(i >> 2) * f.GC * 4 + (i & 3);
+    unsigned long long v = 0ull;
+    for (int c = 0; c < f.GC; ++c) v += g[(size_t)c * 4];
+    f.sub[i] = v;
+}
+
+template <bool GROUPED>
+static void nk_kinetic_pick(const NkDev &d, const NkKinDev &f, int geom, size_t lds, bool bins, unsigned grid, hipStream_t stream) {
+    if (bins) {
+        if (geom == 1) k_kinetic<1, true, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
+        else k_kinetic<2, true, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
+    } else {
+        if (geom == 1) k_kinetic<1, false, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
+        else k_kinetic<2, false, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
+    }
+}
+
+// the dispatch of NK_GEOM_LAUNCH (nk_engine.hip): the geometry mode, the bins and the groups pick the instantiation
 hipError_t nk_kinetic_launch(const NkDev &d, const NkKinDev &f, int geom, size_t lds, bool bins, hipStream_t stream) {
     const int waves = f.nsrc * f.blocks;
     if (waves <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((waves + NK_KIN_WAVES - 1) / NK_KIN_WAVES);
-    if (bins) {
-        if (geom == 1) k_kinetic<1, true><<<grid, NK_WG, lds, stream>>>(d, f);
-        else k_kinetic<2, true><<<grid, NK_WG, lds, stream>>>(d, f);
+    if (f.GC > 0) {
+        nk_kinetic_pick<true>(d, f, geom, lds, bins, grid, stream);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        const int words = f.nsrc * d.S * 4;
+        k_kinetic_fold<<<(unsigned)((words + NK_WG - 1) / NK_WG), NK_WG, 0, stream>>>(f, d.S);
     } else {
-        if (geom == 1) k_kinetic<1, false><<<grid, NK_WG, lds, stream>>>(d, f);
-        else k_kinetic<2, false><<<grid, NK_WG, lds, stream>>>(d, f);
+        nk_kinetic_pick<false>(d, f, geom, lds, bins, grid, stream);
     }
     return hipGetLastError();
 }

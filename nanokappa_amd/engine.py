@@ -93,7 +93,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
            'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info', 'nk_free_paths_columns',
-           'nk_free_paths_map', 'nk_free_paths_map_info', 'nk_kinetic_flights']
+           'nk_free_paths_map', 'nk_free_paths_map_info', 'nk_kinetic_flights', 'nk_kinetic_flights_groups']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -176,6 +176,8 @@ class nk_free_path_map_report(C.Structure):
 
 KIN_MAX_SOURCES = 8          # NK_KIN_MAX_SOURCES (include/nanokappa_hip.h)
 KIN_ROW_WORDS = 32           # NK_KIN_ROW_WORDS
+KIN_MAX_GROUPS = 256         # NK_KIN_MAX_GROUPS
+KIN_MAX_GROUP_WORDS = 1 << 24  # NK_KIN_MAX_GROUP_WORDS
 
 
 class nk_kinetic_args(C.Structure):
@@ -185,6 +187,14 @@ class nk_kinetic_args(C.Structure):
 
 class nk_kinetic_out(C.Structure):
     _fields_ = [('rows', C.POINTER(C.c_int64)), ('sub', C.POINTER(C.c_int64))]
+
+
+class nk_kinetic_groups(C.Structure):
+    _fields_ = [('n_groups', C.c_int32), ('group_of_mode', c_ip)]
+
+
+class nk_kinetic_group_out(C.Structure):
+    _fields_ = [('grp', C.POINTER(C.c_int64))]
 
 
 class nk_kinetic_rays(C.Structure):
@@ -219,15 +229,25 @@ FIELD_TEST_SMALL_BOUND = 2
 _lib = None
 
 
-def load_library():
-    """Load libnanokappa_hip.so; raises NkError with build instructions when it is missing."""
+def load_library(path=None, optional=()):
+    """Load libnanokappa_hip.so; raises NkError with build instructions when it is missing.  path: another build of the library
+    (a developer's A/B run, Engine(library=...)): loaded beside the package's own and not kept; `optional` names entry points that
+    build may lack (one from before they existed) -- calling one of those raises AttributeError."""
     global _lib
+    if path is not None:
+        if not os.path.exists(path):
+            raise NkError('%s not found' % path)
+        return _bind(C.CDLL(path), tuple(optional))
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise NkError('%s not found: build it with `make -C %s` (needs hipcc); there is no CPU fallback'
                       % (LIB_PATH, os.path.join(_HERE, 'csrc')))
-    L = C.CDLL(LIB_PATH)
+    _lib = _bind(C.CDLL(LIB_PATH), ())
+    return _lib
+
+
+def _bind(L, optional):
     L.nk_last_error.restype = C.c_char_p
     L.nk_last_error.argtypes = [C.c_void_p]
     L.nk_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_uint64]
@@ -311,7 +331,9 @@ def load_library():
                                         C.POINTER(nk_free_path_rays), C.POINTER(nk_free_path_columns_report)]
     L.nk_kinetic_flights.argtypes = [C.c_void_p, C.POINTER(nk_kinetic_args), C.POINTER(nk_kinetic_out), C.POINTER(nk_kinetic_rays),
                                      C.POINTER(nk_kinetic_report)]
-    _lib = L
+    if 'nk_kinetic_flights_groups' not in optional or hasattr(L, 'nk_kinetic_flights_groups'):
+        L.nk_kinetic_flights_groups.argtypes = [C.c_void_p, C.POINTER(nk_kinetic_args), C.POINTER(nk_kinetic_groups), C.POINTER(nk_kinetic_out),
+                                                C.POINTER(nk_kinetic_group_out), C.POINTER(nk_kinetic_rays), C.POINTER(nk_kinetic_report)]
     return L
 
 
@@ -400,8 +422,8 @@ def comm_unique_id():
 class Engine(object):
     """One nk_ctx: tables + particle store on one MI355X."""
 
-    def __init__(self, device=0, seed=0):
-        self.L = load_library()
+    def __init__(self, device=0, seed=0, library=None):
+        self.L = library if library is not None else load_library()           # library: load_library(path)'s, for A/B runs
         h = C.c_void_p()
         rc = self.L.nk_create(C.byref(h), int(device), C.c_uint64(int(seed)))
         if rc != 0:
@@ -919,7 +941,7 @@ class Engine(object):
         return self._free_path_map_report(rep)
 
     # ------------------------------------------------------- kinetic flights
-    def kinetic_flights(self, tau, c, n=65536, max_events=0, seed=0, rays=False, rays_per_wave=0, lds_bins=True):
+    def kinetic_flights(self, tau, c, n=65536, max_events=0, seed=0, rays=False, rays_per_wave=0, lds_bins=True, groups=None):
         """Kinetic flights (nk_kinetic_flights; k_kinetic): n energy packets from every 'T' facet, flown, scattered (tau [Q*J], drawn
         in proportion to c / tau, c [Q*J] the volumetric heat capacity per mode), re-emitted by diffuse walls and absorbed by the
         reservoirs -- the steady linearised BTE in the relaxation-time picture (kinetic.py forms conductances and profiles).
@@ -929,7 +951,11 @@ class Engine(object):
         dwell_total [F], per subvolume dwell [F, S] and flux [F, S, 3] (the sum of t v), the raw integers rows [F, 32] and sub
         [F, S, 4] with the report's scales k_*, cdf_scatter, cdf_flux, report; with rays=True also ray_x0 [F, n, 3], ray_mode,
         ray_end (>= 0 the absorbing source, -1 lost, -2 missed, -3 capped), ray_events, ray_casts, ray_D [F, n, 3], ray_dwell and
-        ray_hash [F, n].  Touches neither the particles nor the step counter."""
+        ray_hash [F, n].  Touches neither the particles nor the step counter.
+        groups = (G, table): kinetic groups (nk_kinetic_flights_groups; kinetic_groups.py) -- table [Q*J] holds the group 0 .. G-1
+        of every mode or -1; the result then also holds grp [F, S, G + 1, 4] (int64: sub's words per column, the last column for
+        the modes with -1; the columns add up to sub bit for bit, and everything else is what the call without groups returns),
+        dwell_g [F, S, G + 1] and flux_g [F, S, G + 1, 3].  Without groups the dict and the entry called are the plain ones."""
         from . import kinetic as KN
         n = int(n)
         t, cc = _d(np.ravel(tau)), _d(np.ravel(c))
@@ -957,10 +983,26 @@ class Engine(object):
             pr.mode, pr.end, pr.events, pr.casts = (_p(ro[k], c_ip) for k in ('ray_mode', 'ray_end', 'ray_events', 'ray_casts'))
             pr.hash = _p(ro['ray_hash'], c_u64p)
         rep = nk_kinetic_report()
-        rc = self.L.nk_kinetic_flights(self.h, C.byref(a), C.byref(o), C.byref(pr) if pr else None, C.byref(rep))
+        if groups is None:
+            rc = self.L.nk_kinetic_flights(self.h, C.byref(a), C.byref(o), C.byref(pr) if pr else None, C.byref(rep))
+        else:
+            # (the library refuses a bad G or table by name; only the table's length is checked here, since it reads M entries)
+            G, table = int(groups[0]), groups[1]
+            gs, go = nk_kinetic_groups(), nk_kinetic_group_out()
+            gs.n_groups = G
+            if table is not None:
+                table = np.ascontiguousarray(np.ravel(table), dtype=np.int32)
+                if table.shape[0] != self.M:
+                    raise NkError('kinetic_flights: the group table has %d entries, the material %d modes' % (table.shape[0], self.M))
+                gs.group_of_mode = _p(table, c_ip)
+            GC = G + 1 if 1 <= G <= KIN_MAX_GROUPS else 1
+            grp = np.zeros(min(F * S * GC * 4, KIN_MAX_GROUP_WORDS), dtype=np.int64)     # (a call never returns more words)
+            go.grp = grp.ctypes.data_as(C.POINTER(C.c_int64))
+            rc = self.L.nk_kinetic_flights_groups(self.h, C.byref(a), C.byref(gs), C.byref(o), C.byref(go), C.byref(pr) if pr else None,
+                                                  C.byref(rep))
         r = {k: (list(getattr(rep, k)) if k == 'source_facet' else getattr(rep, k)) for k, _ in nk_kinetic_report._fields_ if k != 'pad_'}
         if rc != 0 and not (rc == ERR_CAPACITY and r['overflow'] > 0):
-            self._ck(rc, 'nk_kinetic_flights')
+            self._ck(rc, 'nk_kinetic_flights' if groups is None else 'nk_kinetic_flights_groups')
         nf = int(rep.n_sources)
         r['source_facet'] = r['source_facet'][:nf]
         r['message'] = self.L.nk_last_error(self.h).decode() if rc != 0 else ''
@@ -970,6 +1012,9 @@ class Engine(object):
                    D=rows[:, 13:16] * 2.0 ** -r['k_D'], D2=rows[:, 16:19] * 2.0 ** -r['k_D2'], dwell_total=rows[:, 19] * 2.0 ** -r['k_T'],
                    dwell=sub[:, :, 0] * 2.0 ** -r['k_t'], flux=sub[:, :, 1:4] * 2.0 ** -r['k_x'], rows=rows, sub=sub,
                    cdf_scatter=cs, cdf_flux=cf, report=r)
+        if groups is not None:
+            grp = grp[:nf * S * GC * 4].reshape(nf, S, GC, 4).copy()
+            out.update(grp=grp, dwell_g=grp[..., 0] * 2.0 ** -r['k_t'], flux_g=grp[..., 1:4] * 2.0 ** -r['k_x'])
         for k, v in ro.items():
             out[k] = v[:nf].copy()
         return out

@@ -47,6 +47,8 @@ def main(argv=None):
     fm_n, fm_kind = free_path_map_option(getattr(args, 'free_path_map', None), fp_n)
     from .kinetic import kinetic_option
     kn_n, kn_T, kn_events = kinetic_option(getattr(args, 'kinetic', None))
+    from .kinetic_groups import kinetic_groups_option, BATCHES_DEFAULT
+    kg_G, kg_kind, kg_axis = kinetic_groups_option(getattr(args, 'kinetic_groups', None), kn_n)
     args = generate_results_folder(args)
     out = None
     # nanokappa.py:34-36 compares the parsed value with 'file'; an explicit `--output file` arrives as the list ['file'] and
@@ -81,13 +83,21 @@ def main(argv=None):
     pop = Population(args, geo, phonons)
     if kn_n > 0:                               # --kinetic N [T] [max_events]: after the set-up, before the first step
         print('Kinetic flights: %d rays per reservoir...' % kn_n)
-        kn = pop.kinetic_flights(n=kn_n, T=kn_T, max_events=kn_events)
+        if kg_G > 0:                           # --kinetic_groups G kind [axis]: the same flights in batches, tallied by group
+            kn = pop.kinetic_flights(n=kn_n, T=kn_T, max_events=kn_events, groups=(kg_G, kg_kind, kg_axis), batches=BATCHES_DEFAULT)
+        else:
+            kn = pop.kinetic_flights(n=kn_n, T=kn_T, max_events=kn_events)
         if kn is not None:
             print('  T = %.2f K: %d sources, %d events, %d casts; %d lost, %d missed, %d cut off' %
                   (kn['T'], len(kn['g']), kn['events'].sum(), kn['casts'].sum(), kn['lost'].sum(), kn['missed'].sum(), kn['capped'].sum()))
             if np.isfinite(kn['kappa_eff']):
                 print('  kappa_eff = %.4f +- %.4f W/m K over L = %g A (bulk %.4f, free-path closed form %.4f W/m K)' %
                       (kn['kappa_eff'], kn['kappa_eff_se'], kn['L'], kn['kappa_bulk'], kn['kappa_free_path']))
+            if kg_G > 0:
+                kg = pop.kinetic_groups_last
+                print('  %d %s groups in %d batches: kappa from the heat flux = %.4f +- %.4f W/m K; per group %s' %
+                      (kg['G'], kg_kind, kg['batches'], float(kg['kappa_flux']), float(kg['kappa_flux_se']),
+                       ' '.join('%.4f' % x for x in kg['kappa_g'][:kg['G']])))
     if fp_n > 0:                               # --free_path N [T] [max_segments]: after the set-up, before the first step
         print('Free-path sampling: %d rays per mode...' % fp_n)
         fp = pop.free_paths(n=fp_n, T=fp_T, max_segments=fp_segments)

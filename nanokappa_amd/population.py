@@ -28,6 +28,7 @@ from . import free_path as FP
 from . import free_sweep as FS
 from . import free_map as FM
 from . import kinetic as KN
+from . import kinetic_groups as KG
 from .engine import Engine
 from .sharding import shard_range
 
@@ -569,14 +570,21 @@ class Population(Constants):
             FP.write_free_path_npz(FP.free_path_npz_path(self.results_folder_name), s)
         return s
 
-    def kinetic_flights(self, n=KN.N_DEFAULT, T=None, tau=None, max_events=KN.MAX_EVENTS_DEFAULT, seed=0, write=True):
+    def kinetic_flights(self, n=KN.N_DEFAULT, T=None, tau=None, max_events=KN.MAX_EVENTS_DEFAULT, seed=0, write=True, groups=None, batches=1):
         """Conductance between the reservoirs and the temperature and heat-flux profile of the steady linearised BTE, by kinetic
         flights on the GPU (Engine.kinetic_flights): n energy packets from every 'T' facet with the lifetimes `tau` [Q*J]
         (default: Phonon.lifetime_function at T, itself by default the mean reservoir temperature) and the heat capacities at T.
         Returns kinetic.summarise()'s dict (G [F, F] in W/K with its standard error, per subvolume dT and q for the geometry's
         reservoir temperatures, kappa_eff between two parallel reservoirs with the bulk value and the free-path closed form
         beside it) and, with a results folder, writes k_kinetic.txt and kinetic.npz.  May be called at any point of a run:
-        particles and step counter are not touched.  With several ranks rank 0 computes and writes; the others return None."""
+        particles and step counter are not touched.  With several ranks rank 0 computes and writes; the others return None.
+        groups = (G, kind[, axis]) or (G, table): kinetic groups (kinetic_groups.py) -- the flights also tally per (subvolume,
+        group of modes); kinetic_groups.summarise_groups()'s dict is kept as `kinetic_groups_last` and written to
+        k_kinetic_groups.txt and kinetic_groups.npz.  batches = B > 1: B engine calls of ceil(n / B) rays per source under the
+        seeds seed, seed + 1, .. (seed 0: the run's), pooled by adding their integers (N = B ceil(n / B)); a group quantity's
+        standard error is the spread over the batches (NaN for B = 1).  batches > 1 without groups pools plain calls the same
+        way: k_kinetic.txt and kinetic.npz of the pooled integers, no group files.  The defaults make the one call and write the
+        files of a call without these arguments."""
         if self.rank != 0:
             return None
         ph, geo = self._ph, self._geo
@@ -585,15 +593,46 @@ class Population(Constants):
         qv = ph.number_of_qpoints * ph.volume_unitcell
         c = KN.heat_capacity(ph.omega, T, qv, self.hbar, self.kb)
         src = KN.source_facets(geo.bound_cond)
-        res = self.engine.kinetic_flights(tau, c, n=int(n), max_events=int(max_events), seed=int(seed))
-        T_f = np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src])
         pair = KN.parallel_pair(src, geo.facets_normal, geo.facets_area, geo.facet_centroid)
+        B = int(batches)
+        if B < 1:
+            raise ValueError('kinetic_flights: batches = %d must be at least 1' % B)
+        per, table, G, kind, edges = None, None, 0, None, None
+        if groups is None and B == 1:
+            res = self.engine.kinetic_flights(tau, c, n=int(n), max_events=int(max_events), seed=int(seed))
+        else:
+            if groups is not None:
+                G = int(groups[0])
+                if isinstance(groups[1], str):
+                    kind = groups[1]
+                    axis = groups[2] if len(groups) > 2 and groups[2] is not None else (pair[2] if pair is not None else 0)
+                    table, G, edges = KG.build(kind, G, ph, tau, ph.group_vel, axis)
+                else:
+                    table = KG.check_table(groups[1], G, np.ravel(ph.omega).shape[0])
+            nb = -(-int(n) // B)
+            # one call: the caller's seed as it is (0 = the engine's own, which is the run's).  Batches need B different, known
+            # seeds: seed, seed + 1, ..; for seed 0 they start at the run's seed, the one the engine would have used
+            seeds = [int(seed)] if B == 1 else [(int(seed) or self.seed) + b for b in range(B)]
+            per = [self.engine.kinetic_flights(tau, c, n=nb, max_events=int(max_events), seed=s_,
+                                               groups=None if table is None else (G, table)) for s_ in seeds]
+            res = per[0] if B == 1 else KG.pool(per)
+        T_f = np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src])
+        omega_c = FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb)
         s = KN.summarise(res, c, ph.group_vel, tau, T, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,
-                         geo.subvol_volume, pair=pair, omega_c=FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb), qv=qv)
+                         geo.subvol_volume, pair=pair, omega_c=omega_c, qv=qv)
         self.kinetic_last = s
+        sg = None
+        if table is not None:
+            sg = KG.summarise_groups(res, c, ph.group_vel, tau, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,
+                                     geo.subvol_volume, table, G, pair=pair, omega_c=omega_c, qv=qv, kind=kind, edges=edges,
+                                     batches=per if B > 1 else None)
+            self.kinetic_groups_last = sg
         if write and self.results_folder_name:
             KN.write_k_kinetic(KN.k_kinetic_path(self.results_folder_name), s)
             KN.write_kinetic_npz(KN.kinetic_npz_path(self.results_folder_name), s)
+            if sg is not None:
+                KG.write_k_kinetic_groups(KG.k_kinetic_groups_path(self.results_folder_name), sg)
+                KG.write_kinetic_groups_npz(KG.kinetic_groups_npz_path(self.results_folder_name), sg)
         return s
 
     def free_path_sweep(self, kind, values, n=FP.N_DEFAULT, T=None, modes=None, max_segments=FP.MAX_SEGMENTS_DEFAULT, w_min=FP.W_MIN_DEFAULT,
