@@ -50,8 +50,7 @@
 // ids) that a wave reads as ONE contiguous piece.  (Round 2 kept six separate arrays: six DRAM streams per wave whose
 // relative placement -- the arrays are 2 MB-aligned allocations, so slot i of every array shares its low address bits --
 // decided the memory system's efficiency: the same binary ran 10-25 % apart from one process to the next.)
-// blk = distance between two blocks in units of T; slot i lives at p[(i / 64) * blk + i % 64].  blk = 64 with separate
-// base pointers gives back the plain arrays (NK_LAYOUT=soa, developer comparison).
+// blk = distance between two blocks in units of T; slot i lives at p[(i / 64) * blk + i % 64].
 template <class T>
 struct NkField {
     T *p;
@@ -1018,16 +1017,11 @@ __device__ __forceinline__ void nk_reflect(const NkDev &d, const NkSvTab &tb, in
     const double *roul = d.roulette + (int64_t)rough_idx * d.M;
     const uint8_t ts = d.true_spec[idx];
     const double sp = d.specularity[idx];
-#ifndef NK_REFLECT_LAZY
     const int smap = d.spec_map[idx];
     const int lo = lut[kb], hi = lut[kb + 1];
     const double rlast = roul[d.M - 1];
-#endif
     const bool spec = ts && (r_spec <= sp);
     if (spec) {
-#ifdef NK_REFLECT_LAZY
-        const int smap = d.spec_map[idx];
-#endif
         int out = smap;
         if (d.degen_j2) {
             int j2 = d.degen_j2[out];
@@ -1035,10 +1029,6 @@ __device__ __forceinline__ void nk_reflect(const NkDev &d, const NkSvTab &tb, in
         }
         mode_out = out; n_out = n_in; omega_out = omega_in; E0_out = E0_in;
     } else {
-#ifdef NK_REFLECT_LAZY
-        const int lo = lut[kb], hi = lut[kb + 1];
-        const double rlast = roul[d.M - 1];
-#endif
         const double r = r_diff * rlast;
         // np.searchsorted(roulette, r) (Population.py:1005) through a bucket index: r_diff in [k, k+1) / roul_nlut brackets
         // the answer between two precomputed positions a few entries apart; up to four of them are read in one go (same

@@ -28,8 +28,7 @@
 #include "nk_freepath.h"
 #include "nk_freecols.h"
 #include "nk_kinetic.h"
-// instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there; -DNK_PLAIN_IN_ENGINE: here, for comparisons)
-#ifndef NK_PLAIN_IN_ENGINE
+// instantiated in nk_sweep_plain.hip (compiled with the machine LICM on; see there)
 extern template __global__ void k_sweep<1, false, false, false, false, true, 1>(NkDev, uint32_t, int, int);
 extern template __global__ void k_sweep<1, false, false, false, false, true, 2>(NkDev, uint32_t, int, int);
 extern template __global__ void k_sweep<1, false, false, false, false, false, 1>(NkDev, uint32_t, int, int);
@@ -38,7 +37,6 @@ extern template __global__ void k_sweep<1, false, false, false, false, true, 1, 
 extern template __global__ void k_sweep<1, false, false, false, false, true, 2, true>(NkDev, uint32_t, int, int);
 extern template __global__ void k_sweep<1, false, false, false, false, false, 1, true>(NkDev, uint32_t, int, int);
 extern template __global__ void k_sweep<1, false, false, false, false, false, 2, true>(NkDev, uint32_t, int, int);
-#endif
 
 struct NkRccl {      // symbols resolved lazily with dlopen: a single-GPU run never loads librccl
     void *lib = nullptr;
@@ -245,7 +243,7 @@ static int nk_field_upload(nk_ctx *ctx, const NkDev &d, const NkField<T> &f, con
 
 // 1 = ray-casting tables fit LDS, 2 = they stay in global memory
 static inline int nk_geom_mode(const nk_ctx *ctx) { return (ctx->d.F <= NK_LDS_FACES && ctx->d.Fc <= NK_LDS_FACES) ? 1 : 2; }
-// kind: 0 plain, 1 k_emit (emission scratch), 2 / 3 k_sweep (mode records, output ring without / with ids)
+// kind: 0 plain, 1 k_emit (emission scratch), 2 / 3 k_sweep (mode records, carry without / with ids)
 static inline bool nk_want_split(const nk_ctx *ctx);
 static inline size_t nk_lds(const nk_ctx *ctx, bool geom, int kind = 0) {
     const NkDev &d = ctx->d;

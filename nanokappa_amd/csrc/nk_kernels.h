@@ -40,18 +40,6 @@
 #include "nk_device.h"
 
 #define NK_TILE 64           // particles per tile = lanes of a wave
-// NK_NT=1 builds the sweep's particle loads / stores as non-temporal accesses (developer comparison; measured SLOWER on
-// MI355X: k_sweep 0.29-0.32 ms against 0.263-0.267 ms with plain accesses at 1e7 particles, profiles/r02_notes.txt).
-#ifndef NK_NT
-#define NK_NT 0
-#endif
-#if NK_NT
-#define NK_LD(p) __builtin_nontemporal_load(p)
-#define NK_ST(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define NK_LD(p) (*(p))
-#define NK_ST(p, v) (*(p) = (v))
-#endif
 // Developer build (make stamps -> libnanokappa_hip_stamps.so, env NK_STAMPS=1): s_memtime stamps around the sections of
 // the sweep's tile loop, summed per wave; shares only (the stamps' waits forbid overlaps the real kernel has).
 #ifdef NK_STAMPS
@@ -89,28 +77,16 @@ struct NkLds {
     double *lrec;
     // the sweep's carry: up to 64 parked particles per wave
     double *carry;
-    // output ring of the sweep, NK_ORING particles per wave: x y z occ nts [pid] (doubles), then w0
-    double *oring;
-    unsigned int *oring_w;
     double *colsum;                      // k_resident: column sums of the tally rows
 };
 
 // geom: 0 = no ray-casting tables, 1 = planes/faces/facets staged in LDS, 2 = read from global memory (large meshes)
 // nrf: faces of the reservoir sampling tables staged in LDS (0 = not staged); kind: 0 plain, 1 + k_emit's scratch,
-// 2 + the sweep's mode records (nlrec per wave), carry (unless the sweep is split) and output ring, 3 the same with particle ids,
+// 2 + the sweep's mode records (nlrec per wave), carry (unless the sweep is split), 3 the same with particle ids,
 // 4 / 5 = 2 / 3 + k_emit's scratch + a column-sum area (the resident kernel of small ensembles, k_resident, does both)
-#ifndef NK_LREC_STRIDE
-#define NK_LREC_STRIDE 5     // 16-byte units between the LDS copies of two mode records: 4 = packed (64 B), 5 spreads the banks
-#endif
-#ifndef NK_OUT_RING
-#define NK_OUT_RING 0        // 1: finished particles go through an LDS ring and leave in whole aligned tiles (NkOut below)
-#endif
-#define NK_ORING (NK_OUT_RING ? 128 : 0)
+#define NK_LREC_STRIDE 5     // 16-byte units between the LDS copies of two mode records: 64 B of record, then 16 B that hold its mode and spread the banks
 // doubles of one wave's carry: x y z occ nts cts (64 each), w0 + evc (64 words each); with ids: + pid (64), gm and slot (64 words each)
 #define NK_CARRY_DOUBLES(kind) (((kind) == 3 || (kind) == 5) ? 576 : 448)
-#ifndef NK_BOX_GENERAL_CAST
-#define NK_BOX_GENERAL_CAST 0    // 1: the box store's event pass casts its rays through the general search over the LDS planes (developer probe)
-#endif
 #define NK_COLSUM_DOUBLES 768   // k_resident: column sums of the tally rows, two halves (NB <= 384)
 __host__ __device__ inline size_t nk_lds_bytes(int S, int R, int F, int NP, int Fc, int geom, int kind, int nrf, int rbfP, int nlrec = 0, int carry = 0) {
     const bool emit = kind == 1 || kind >= 4;
@@ -119,10 +95,10 @@ __host__ __device__ inline size_t nk_lds_bytes(int S, int R, int F, int NP, int 
     int Fcl = geom == 1 ? Fc : 0;
     size_t nd = (size_t)S + (size_t)((rbfP + 1) & ~1) + 3 * S + ((3 * S) & 1) + 4 * (size_t)S + NK_NREP * S + NK_NREP * 3 * S + 4 * R +
                 (size_t)Fl * NK_FACE_DOUBLES + (size_t)Pl * NK_PLANE_DOUBLES + 2 * (size_t)R + 10 * (size_t)nrf +
-                (emit ? 2 * (size_t)(NK_WG / 64) * NK_EMIT_CHUNK : 0) + (kind >= 2 ? (size_t)(NK_WG / 64) * ((size_t)nlrec * 2 * NK_LREC_STRIDE + (carry ? NK_CARRY_DOUBLES(kind) : 0) + NK_ORING * ((kind == 3 || kind == 5) ? 6 : 5)) : 0) +
+                (emit ? 2 * (size_t)(NK_WG / 64) * NK_EMIT_CHUNK : 0) + (kind >= 2 ? (size_t)(NK_WG / 64) * ((size_t)nlrec * 2 * NK_LREC_STRIDE + (carry ? NK_CARRY_DOUBLES(kind) : 0)) : 0) +
                 (kind >= 4 ? NK_COLSUM_DOUBLES : 0) + 4;
     size_t bytes = nd * 8 + (size_t)Fcl * sizeof(NkFacet) +
-                   (size_t)(NK_NREP * S + R + 1 + (R + 1) + (emit ? 3 * (NK_WG / 64) * NK_EMIT_CHUNK : 0) + (kind >= 2 ? (NK_WG / 64) * NK_ORING : 0)) * 4 + 32;
+                   (size_t)(NK_NREP * S + R + 1 + (R + 1) + (emit ? 3 * (NK_WG / 64) * NK_EMIT_CHUNK : 0)) * 4 + 32;
     return (bytes + 15) & ~(size_t)15;
 }
 
@@ -155,8 +131,7 @@ __device__ __forceinline__ void nk_lds_carve(const NkDev &d, unsigned char *smem
     if (KIND >= 2) {
         L.lrec = p; p += (NK_WG / 64) * (size_t)d.nlrec * 2 * NK_LREC_STRIDE;
         L.carry = p; p += d.qx ? 0 : (NK_WG / 64) * NK_CARRY_DOUBLES(KIND);
-        L.oring = p; p += (NK_WG / 64) * NK_ORING * ((KIND == 3 || KIND == 5) ? 6 : 5);
-    } else { L.lrec = nullptr; L.carry = nullptr; L.oring = nullptr; }
+    } else { L.lrec = nullptr; L.carry = nullptr; }
     if (KIND >= 4) { L.colsum = p; p += NK_COLSUM_DOUBLES; } else L.colsum = nullptr;
     NkFacet *facets = (NkFacet *)p;
     unsigned int *u = (unsigned int *)(facets + Fcl);
@@ -169,7 +144,6 @@ __device__ __forceinline__ void nk_lds_carve(const NkDev &d, unsigned char *smem
         L.sp_cnt = u; u += (NK_WG / 64) * NK_EMIT_CHUNK;
         L.sp_rm = u; u += (NK_WG / 64) * NK_EMIT_CHUNK;
     } else { L.sp_pref = L.sp_cnt = L.sp_rm = nullptr; }
-    if (KIND >= 2) { L.oring_w = u; u += (NK_WG / 64) * NK_ORING; } else L.oring_w = nullptr;
     L.resT = resT;
     L.rf_off = rf_off; L.rf_cdf = rf_cdf; L.rf_verts = rf_verts;
     if (GEOM == 1) { L.faces = faces; L.planes = planes; L.facets = facets; }
@@ -625,24 +599,15 @@ __global__ __launch_bounds__(NK_WG) void k_emit(NkDev d, uint32_t step) {
     nk_emit_body<GEOM, BOX>(d, step, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// Output ring of a sweep wave: finished particles are staged in LDS and leave for HBM in whole, aligned tiles of 64 --
-// every store instruction then writes full cache lines.  (Storing each tile's survivors where the write cursor stands
-// writes ragged pieces; the partly written lines at their ends are first fetched from HBM: measured 0.14 GB of reads per
-// step on top of the 0.44 GB the particles themselves need.)
+// Write cursor of a sweep wave: finished particles go back into the wave's own segment, compacted, each tile's survivors
+// where the cursor stands.  The fused sweep stores them at the tile's commit (push); the split sweep takes their slots at the
+// commit (reserve) and issues the stores one turn later (store), behind the wait for the next tile.
 template <bool PID>
 struct NkOut {
-    double *x, *y, *z, *occ, *nts, *pid;
-    unsigned int *w0;
-    int on, ob, wout;            // staged particles, ring position of the oldest, particles already in HBM
+    int wout;                    // slots taken so far
     int64_t m0; int ms, mroom;   // the o-th finished particle goes to slot m0 + ms * o (ms = -1: a DOWN sweep, NkDev::down), o < mroom
-    __device__ __forceinline__ void place(int64_t first, int sign, int room) { m0 = first; ms = sign; mroom = room; }
-    __device__ __forceinline__ void init(const NkLds &L, int wave) {
-        double *p = L.oring + wave * NK_ORING * (PID ? 6 : 5);
-        x = p; y = p + NK_ORING; z = p + 2 * NK_ORING; occ = p + 3 * NK_ORING; nts = p + 4 * NK_ORING; pid = PID ? p + 5 * NK_ORING : nullptr;
-        w0 = L.oring_w + wave * NK_ORING;
-        on = ob = wout = 0;
-    }
-    // the same in two halves (plain cursor only): the slots are taken now, the stores are issued later (the sweep's tile commit)
+    __device__ __forceinline__ void place(int64_t first, int sign, int room) { wout = 0; m0 = first; ms = sign; mroom = room; }
+    // lanes with a finished particle take their slots (rank = position among them, n = how many)
     __device__ __forceinline__ int reserve(int rank, int n) { const int o = wout + rank; wout += n; return o; }
     // one slot's fields from ONE address (NkBlock): the stores differ by immediate offsets
     template <bool BOX>
@@ -650,54 +615,26 @@ struct NkOut {
                                                     uint32_t pw0, unsigned long long ppid) {
         typedef NkBlock<!BOX, PID> B;
         double *q = B::slot(d.x.p, i);
-        NK_ST(q, px); NK_ST(q + B::O_Y, py); NK_ST(q + B::O_Z, pz); NK_ST(q + B::O_OCC, pocc);
-        if (!BOX) NK_ST(q + B::O_NTS, pnts);
-        if (PID) NK_ST(reinterpret_cast<unsigned long long *>(q + B::O_PID), ppid);
-        NK_ST(B::word(d.x.p, i), pw0);
+        *q = px; q[B::O_Y] = py; q[B::O_Z] = pz; q[B::O_OCC] = pocc;
+        if (!BOX) q[B::O_NTS] = pnts;
+        if (PID) *reinterpret_cast<unsigned long long *>(q + B::O_PID) = ppid;
+        *B::word(d.x.p, i) = pw0;
     }
+    // lanes with `put` store their particle in the slot `o` they took
     template <bool BOX = false>
-    __device__ __forceinline__ void store(const NkDev &d, int64_t base, bool put, int o, double px, double py, double pz, double pocc,
-                                          double pnts, uint32_t pw0, unsigned long long ppid) {
+    __device__ __forceinline__ void store(const NkDev &d, bool put, int o, double px, double py, double pz, double pocc, double pnts,
+                                          uint32_t pw0, unsigned long long ppid) {
         if (put) {
             if (o < mroom) put_slot<BOX>(d, m0 + ms * (int64_t)o, px, py, pz, pocc, pnts, pw0, ppid);
             else atomicOr(d.overflow, 2);     // segment full
         }
     }
-    // lanes with `put` append their particle (rank = position among them, n = how many); a full tile leaves at once
+    // both at once (the cursor moves after the stores, not store(reserve()): the compiler schedules the two orders differently)
     template <bool BOX = false>
-    __device__ __forceinline__ void push(const NkDev &d, int64_t base, int lane, bool put, int rank, int n, double px, double py,
-                                         double pz, double pocc, double pnts, uint32_t pw0, unsigned long long ppid) {
-        if (!NK_OUT_RING) {                           // straight to the write cursor
-            if (put) {
-                const int o = wout + rank;
-                if (o < mroom) put_slot<BOX>(d, m0 + ms * (int64_t)o, px, py, pz, pocc, pnts, pw0, ppid);
-                else atomicOr(d.overflow, 2);     // segment full
-            }
-            wout += n;
-            return;
-        }
-        if (put) {
-            const int e = (ob + on + rank) & (NK_ORING - 1);
-            x[e] = px; y[e] = py; z[e] = pz; occ[e] = pocc; nts[e] = pnts; w0[e] = pw0;
-            if (PID) pid[e] = __longlong_as_double((long long)ppid);
-        }
-        on += n;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (on >= NK_TILE) flush(d, base, lane, NK_TILE);
-    }
-    __device__ __forceinline__ void flush(const NkDev &d, int64_t base, int lane, int n) {
-        if (wout + n <= d.segcap) {
-            if (lane < n) {
-                const int e = (ob + lane) & (NK_ORING - 1);
-                const int64_t i = base + wout + lane;
-                d.x[i] = x[e]; d.y[i] = y[e]; d.z[i] = z[e]; d.occ[i] = occ[e]; d.nts[i] = nts[e]; d.w0[i] = w0[e];
-                if (PID) d.pid[i] = (unsigned long long)__double_as_longlong(pid[e]);
-            }
-            wout += n;
-        } else if (lane == 0) atomicOr(d.overflow, 2);      // segment full: the tile is dropped
-        ob = (ob + n) & (NK_ORING - 1);
-        on -= n;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __device__ __forceinline__ void push(const NkDev &d, bool put, int rank, int n, double px, double py, double pz, double pocc,
+                                         double pnts, uint32_t pw0, unsigned long long ppid) {
+        store<BOX>(d, put, wout + rank, px, py, pz, pocc, pnts, pw0, ppid);
+        wout += n;
     }
 };
 
@@ -730,18 +667,6 @@ __device__ __forceinline__ NkLdsRec nk_lds_rec(const double2 *q) { return (NkLds
 // (coalesced, one extra round trip for those particles) and k_events runs the events, whose tree walks are chains of
 // dependent loads, at twice the residency; the fused form keeps the events in registers (boxes: a third of the particles
 // have one every step, a second trip through HBM would cost more than the residency gains).
-#ifndef NK_PREFETCH2
-#define NK_PREFETCH2 0
-#endif
-#ifndef NK_PARK_TAU
-#define NK_PARK_TAU 1           // the sweep keeps the lifetime window's five doubles in vector registers (NkTauWin)
-#endif
-#ifndef NK_PRIO_ROT
-#define NK_PRIO_ROT 0           // log2 of the tiles between two steps of the sweep's issue-priority rotation (0 = off)
-#endif
-#ifndef NK_DEFER_STORE
-#define NK_DEFER_STORE 0      // measured: no gain (profiles/r03_notes.txt); the switch stays in the source
-#endif
 #ifndef NK_SWEEP_OCC_BIG
 #define NK_SWEEP_OCC_BIG 2      // the variants with rough facets, RBF temperatures or large meshes (more than 168 VGPRs)
 #endif
@@ -770,7 +695,7 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
                                               , unsigned long long st_entry_r
 #endif
 ) {
-    static_assert(!BOX || (GEOM == 1 && !SPLIT && !NK_PREFETCH2 && !NK_OUT_RING), "the box store goes with the fused sweep over LDS tables");
+    static_assert(!BOX || (GEOM == 1 && !SPLIT), "the box store goes with the fused sweep over LDS tables");
     const bool do_flux = (flags & 1) != 0;          // flags: 1 = heat-flux step
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: segment bookkeeping lives in scalar registers
     const int rep = lane & (NK_NREP - 1);
@@ -778,16 +703,13 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
     NkBoxWalls bw;
     if (BOX) bw.load(d);
     NkTauWin tw;
-    tw.load(d, NK_PARK_TAU != 0);
+    tw.load(d, true);                               // the lifetime window's five doubles stay in vector registers
     double2 *lrec = reinterpret_cast<double2 *>(L.lrec) + wave * d.nlrec * NK_LREC_STRIDE;
     // the wave's carry in LDS: x y z occ nts cts [64] each, then (ids) pid [64], then the words w0, evc and (ids) gm [64] each
     double *const cX = L.carry ? L.carry + wave * NK_CARRY_DOUBLES(PID ? 3 : 2) : nullptr;
     double *const cP = cX + 6 * 64;
     uint32_t *const cW = reinterpret_cast<uint32_t *>(cX + (PID ? 7 : 6) * 64);
     const int nwaves = nwg * (NK_WG / 64);
-#if NK_PRIO_ROT
-    const int prio_phase = (int)(wg / (nwg > 3 ? (nwg + 3) / 4 : 1));     // quarter of the grid = dispatch age
-#endif
     for (int seg = wg * (NK_WG / 64) + wave; seg < d.nseg; seg += nwaves) {
         const int64_t base = (int64_t)seg * d.segcap;
         const int nnew = d.R > 0 ? d.seg_new[seg] : 0;
@@ -801,13 +723,13 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
                 const double4 a = g[0], b = g[1];
                 double2 *q = lrec + r0 * NK_LREC_STRIDE;
                 q[0] = make_double2(a.x, a.y); q[1] = make_double2(a.z, a.w); q[2] = make_double2(b.x, b.y); q[3] = make_double2(b.z, b.w);
-                if (NK_LREC_STRIDE > 4 && (ROUGH || PID)) *reinterpret_cast<int *>(q + 4) = sm.mode(r0);   // the mode itself, in the record's spare 16 bytes
+                if (ROUGH || PID) *reinterpret_cast<int *>(q + 4) = sm.mode(r0);   // the mode itself, in the record's spare 16 bytes
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         }
         // global mode of a stored index: from the LDS copy of the record where there is one (no memory access in the tile loop)
         auto mode_of = [&](int i) -> int {
-            if (use_lrec && NK_LREC_STRIDE > 4) return *(const __attribute__((address_space(3))) int *)(const void *)(lrec + i * NK_LREC_STRIDE + 4);
+            if (use_lrec) return *(const __attribute__((address_space(3))) int *)(const void *)(lrec + i * NK_LREC_STRIDE + 4);
             return sm.mode(i);
         };
         // the slots that hold the segment's particles, [lo, hi) of its range, and the order of the walk (NkDev::seg_lo / down): tiles
@@ -820,7 +742,6 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
         // an UP sweep packs upwards from lo -- from 0 once lo has used up half of the head room; a DOWN sweep downwards from hi - 1
         const int wlo = (!down && lo > (d.segcap - count) / 2) ? 0 : lo;
         NkOut<PID> O;                                 // finished particles on their way back to the segment
-        O.init(L, wave);
         O.place(down ? base + hi - 1 : base + wlo, down ? -1 : 1, down ? count : d.segcap - wlo);
         int qn = SPLIT ? d.seg_evq[seg] : 0;          // SPLIT: entries in the segment's event queue (k_emit may have put the entering particles there:
         if (SPLIT && lane == 0 && qn > 0) atomicAdd(&L.bins.misc[0], (unsigned int)qn);     //  they count as "emitted" here)
@@ -830,22 +751,24 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
         const unsigned long long st_c0 = st_last, st_r0 = __builtin_amdgcn_s_memrealtime();   // shader clock against the 100 MHz counter
 #endif
-        // The tiles come through two register sets that take turns (NkTileBuf): a set is read once its tile has arrived and at once
-        // refilled with the tile two turns ahead (NK_PREFETCH2; else one set, one tile ahead).  Nothing ever copies a set that a
-        // load is still to fill -- such a copy waits for that load, which is what made an earlier "second prefetched tile" (one set
-        // shifted into the other every iteration) a second tile in name only: the compiler had to drain the counter at the top of
-        // every iteration (s_waitcnt vmcnt(0)).  Every turn issues the same loads (beyond the segment's particles the address is
-        // clamped into its slots and the lanes are masked), after the deferred stores of the previous turn: "all but the newest
-        // loads" (vmcnt(6), (7) with ids) then leaves exactly the other set's tile in flight.
-        constexpr bool PF2 = NK_PREFETCH2 || SPLIT;
-        constexpr bool DEFER = (NK_DEFER_STORE || PF2) && !NK_OUT_RING;
+        // The tiles come through register sets (NkTileBuf).  The FUSED sweep has one set and runs one tile ahead: plain loads that the
+        // compiler counts itself, of the lanes that will be used only.  The SPLIT sweep has two sets that take turns and runs two
+        // tiles ahead: a set is read once its tile has arrived and at once refilled with the tile two turns ahead.  Nothing ever
+        // copies a set that a load is still to fill -- such a copy waits for that load, which is what made an earlier "second
+        // prefetched tile" (one set shifted into the other every iteration) a second tile in name only: the compiler had to drain
+        // the counter at the top of every iteration (s_waitcnt vmcnt(0)).  Every turn of the split sweep issues the same loads
+        // (beyond the segment's particles the address is clamped into its slots and the lanes are masked), after the held stores of
+        // the previous turn: "all but the newest loads" (vmcnt(6), (7) with ids) then leaves exactly the other set's tile in flight.
         struct NkTileBuf { uint32_t w0; double x, y, z, occ, nts; unsigned long long pid; };
+        // what the split sweep holds back of a tile for one turn: its finished particles (done: slot o of the write cursor) and its
+        // event particles (ev: entry q of the queue) -- a particle is one or the other, so one set of values serves both
+        struct NkHeld { bool done, ev; int o, q; double x, y, z, occ, nts; uint32_t w0; unsigned long long pid; };
         NkTileBuf bA = {0u, 0, 0, 0, 0, 0, 0ull}, bB = bA;
         auto fetch = [&](NkTileBuf &b, int r) {
             int rr = down ? bhi - r : blo + r;                    // r = 64 x the tile's number in the walk
             rr = rr < 0 ? 0 : (rr < d.segcap - NK_TILE ? rr : d.segcap - NK_TILE);
             const int64_t i0 = base + rr;
-            if (PF2) {
+            if (SPLIT) {
                 // Loads the compiler does not know to be loads: it keeps the memory counter itself, and with the event pass's loops
                 // and branches between a load and its use it gives up and drains the counter (vmcnt(0)) at the top of every turn.
                 // These leave the counting to `arrived` below.  What the compiler issues itself only makes its own waits stricter
@@ -867,49 +790,31 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
             if (rr + lane >= lo && rr + lane < hi && r < nA * NK_TILE) {   // (one tile ahead, the compiler's own counting: only what will be used)
                 typedef NkBlock<!BOX, PID> B;
                 const double *q = B::tile(d.x.p, i0, lane);     // ONE address; the fields at immediate offsets
-                b.w0 = NK_LD(B::word(d.x.p, i0) + lane); b.x = NK_LD(q); b.y = NK_LD(q + B::O_Y); b.z = NK_LD(q + B::O_Z); b.occ = NK_LD(q + B::O_OCC);
-                if (!BOX) b.nts = NK_LD(q + B::O_NTS);
-                if (PID) b.pid = NK_LD(reinterpret_cast<const unsigned long long *>(q + B::O_PID));
+                b.w0 = B::word(d.x.p, i0)[lane]; b.x = *q; b.y = q[B::O_Y]; b.z = q[B::O_Z]; b.occ = q[B::O_OCC];
+                if (!BOX) b.nts = q[B::O_NTS];
+                if (PID) b.pid = *reinterpret_cast<const unsigned long long *>(q + B::O_PID);
             }
         };
-        // the set's tile is there: everything but the loads issued last -- the other set's -- has retired
+        // split: the set's tile is there -- everything but the loads issued last, the other set's, has retired
         auto arrived = [&](NkTileBuf &b) {
-            if (!PF2) return;
+            if (!SPLIT) return;
             if (PID) asm volatile("s_waitcnt vmcnt(7)" : "+v"(b.w0), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.occ), "+v"(b.nts), "+v"(b.pid) : : "memory");
             else asm volatile("s_waitcnt vmcnt(6)" : "+v"(b.w0), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.occ), "+v"(b.nts) : : "memory");
         };
         auto drained = [&](NkTileBuf &b) {
-            if (PF2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(b.w0), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.occ), "+v"(b.nts), "+v"(b.pid) : : "memory");
+            if (SPLIT) asm volatile("s_waitcnt vmcnt(0)" : "+v"(b.w0), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.occ), "+v"(b.nts), "+v"(b.pid) : : "memory");
         };
         fetch(bA, 0);
-        if (PF2) fetch(bB, NK_TILE);
-        // The finished particles of a tile are STORED at the top of the next iteration, between the wait for that iteration's
-        // tile and the next prefetch (NK_DEFER_STORE): a wave's memory counter retires in order, so the wait for a tile also
-        // waits for every store issued after its loads -- stores issued at the end of the previous iteration are the youngest
-        // operations in the queue and their acknowledgement is a full memory round trip; issued an iteration earlier they
-        // have long retired.  Their slots are taken at once (reserve), so the event pass appends behind them as before.
-        bool sdone = false, sev = false;
-        int so = 0, sq = 0;
-        double sx = 0, sy = 0, sz = 0, socc = 0, snts = 0;
-        uint32_t sw0 = 0u;
-        unsigned long long spid = 0;
+        if (SPLIT) fetch(bB, NK_TILE);
+        // The fused sweep stores a tile's finished particles at its commit.  The split sweep STORES them at the top of the next
+        // turn, between the wait for that turn's tile and the next prefetch: a wave's memory counter retires in order, so the
+        // hand-counted wait for a tile also waits for every store issued after its loads -- stores issued at the end of the
+        // previous turn are the youngest operations in the queue and their acknowledgement is a full memory round trip; issued a
+        // turn earlier they have long retired.  Their slots are taken at once (reserve), and so are their places in the queue.
+        NkHeld held = {false, false, 0, 0, 0, 0, 0, 0, 0, 0u, 0ull};
         auto turn = [&](NkTileBuf &buf, const int t) __attribute__((always_inline)) {
             const bool flush = t == nA;               // one empty tile: drains the carry
             arrived(buf);
-#if NK_PRIO_ROT
-            // The SIMD's issue arbiter prefers the OLDEST wave: of the workgroups resident on a CU the first-dispatched one runs
-            // ahead and the last one behind (stamps: tile loops of 155 / 165 / 179 / 196 us by quarter of the grid for equal
-            // work), and a sweep ends with its slowest wave.  Every wave therefore rotates its issue priority with the tiles,
-            // the phase taken from its workgroup's position in the dispatch order: over a segment every wave has held every level.
-            if ((t & ((1 << NK_PRIO_ROT) - 1)) == 0) {
-                switch (((t >> NK_PRIO_ROT) + prio_phase) & 3) {
-                    case 0: __builtin_amdgcn_s_setprio(0); break;
-                    case 1: __builtin_amdgcn_s_setprio(1); break;
-                    case 2: __builtin_amdgcn_s_setprio(2); break;
-                    default: __builtin_amdgcn_s_setprio(3); break;
-                }
-            }
-#endif
             bool act = false;
             double x = 0, y = 0, z = 0, occ = 0, nts = 0, omega = 0, E0 = 0, vx = 0, vy = 0, vz = 0;
             uint32_t w0 = 0u;
@@ -920,23 +825,23 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
                 { const int rr = down ? bhi - r : blo + r; act = rr + lane >= lo && rr + lane < hi; }
                 w0 = buf.w0; x = buf.x; y = buf.y; z = buf.z; occ = buf.occ; nts = buf.nts; pid = buf.pid;
             }
-            if (DEFER) {                                // the previous tile's finished particles leave now
+            if (SPLIT) {                                // the previous tile's finished particles leave now
                 asm volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(occ), "+v"(nts), "+v"(w0));   // behind the wait for this tile
-                O.template store<BOX>(d, base, sdone, so, sx, sy, sz, socc, snts, sw0, spid);
-                sdone = false;
-                if (SPLIT && sev) {                     // ... and its event particles, for the queue
-                    if (sq < d.segcap) {
-                        const int64_t i = base + sq;
-                        d.qx[i] = sx; d.qy[i] = sy; d.qz[i] = sz; d.qocc[i] = socc; d.qnts[i] = snts; d.qw0[i] = sw0;
-                        if (PID) d.qpid[i] = spid;
+                O.template store<BOX>(d, held.done, held.o, held.x, held.y, held.z, held.occ, held.nts, held.w0, held.pid);
+                held.done = false;
+                if (held.ev) {                          // ... and its event particles, for the queue
+                    if (held.q < d.segcap) {
+                        const int64_t i = base + held.q;
+                        d.qx[i] = held.x; d.qy[i] = held.y; d.qz[i] = held.z; d.qocc[i] = held.occ; d.qnts[i] = held.nts; d.qw0[i] = held.w0;
+                        if (PID) d.qpid[i] = held.pid;
                     }
                 }
-                sev = false;
+                held.ev = false;
+                fetch(buf, (t + 2) * NK_TILE);          // every turn, also the empty one: the count of loads in flight is fixed
             }
-            if (PF2) fetch(buf, (t + 2) * NK_TILE);   // every turn, also the empty one: the count of loads in flight is fixed
             if (!flush) {
                 const int r = t * NK_TILE;
-                if (!PF2) fetch(buf, r + NK_TILE);
+                if (!SPLIT) fetch(buf, r + NK_TILE);
                 const bool newborn = (w0 & NK_NEWBORN) != 0u;
                 w0 &= ~NK_NEWBORN;
                 const int idx = act ? (int)(w0 & lbmask) : 0;
@@ -969,21 +874,13 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
             const bool done = act && !ev;
             const unsigned long long mD = __ballot(done), mE = __ballot(ev);
             if (done) nk_tally_one(d, L.tb, L.bins, x, y, z, occ, omega, E0, vx, vy, vz, do_flux, rep);
-            if (DEFER) {
-                so = O.reserve(nk_rank(mD), __popcll(mD));
-                sdone = done; sx = x; sy = y; sz = z; socc = occ; snts = nts; sw0 = w0; spid = pid;
-            } else O.template push<BOX>(d, base, lane, done, nk_rank(mD), __popcll(mD), x, y, z, occ, nts, w0, pid);
+            if (SPLIT) {
+                held.o = O.reserve(nk_rank(mD), __popcll(mD));
+                held.done = done; held.x = x; held.y = y; held.z = z; held.occ = occ; held.nts = nts; held.w0 = w0; held.pid = pid;
+            } else O.template push<BOX>(d, done, nk_rank(mD), __popcll(mD), x, y, z, occ, nts, w0, pid);
             NK_STAMP(2);
-            if (SPLIT) {                               // the tile's event particles leave for the queue; k_events takes over
-                if (DEFER) { sev = ev; sq = qn + nk_rank(mE); }     // (a particle is final or has an event: the same held values)
-                else if (ev) {
-                    const int o = qn + nk_rank(mE);
-                    if (o < d.segcap) {
-                        const int64_t i = base + o;
-                        d.qx[i] = x; d.qy[i] = y; d.qz[i] = z; d.qocc[i] = occ; d.qnts[i] = nts; d.qw0[i] = w0;
-                        if (PID) d.qpid[i] = pid;
-                    }
-                }
+            if (SPLIT) {                               // the tile's event particles leave for the queue a turn later; k_events takes over
+                held.ev = ev; held.q = qn + nk_rank(mE);
                 qn += __popcll(mE);
                 return;
             }
@@ -1045,7 +942,7 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
                 // box store: a particle's FIRST event of the step is the wall it lies beyond (the carry holds no hit for it yet)
                 if (BOX && eact && evc == 0u) nk_box_first_hit(bw, d.inv_dt, p.x, p.y, p.z, p.vx, p.vy, p.vz, p.nts, p.facet);
                 if (eact) st = nk_event_one<ROUGH, RBF>(d, GEOM == 2 ? d.NG : 0, L.planes, L.faces, L.facets, L.tb, L.resT, L.bins, p, cts, evc, cpid, step,
-                                                        (BOX && !NK_BOX_GENERAL_CAST) ? &bw : nullptr);
+                                                        BOX ? &bw : nullptr);
                 const bool alive = eact && st == NK_EV_DONE, more = eact && st == NK_EV_MORE;
 #ifdef NK_STAMPS
                 { const double fence_ = p.x + p.nts; asm volatile("" ::"v"(fence_)); }
@@ -1064,7 +961,7 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
                 const uint32_t w0s = BOX ? (idxe | (p.facet < 0 ? NK_LOST : 0u)) : w0e;  // what the store keeps
                 const bool home = alive && stay, away = alive && !stay;
                 const unsigned long long mA = __ballot(home), mM = __ballot(more);
-                O.template push<BOX>(d, base, lane, home, nk_rank(mA), __popcll(mA), p.x, p.y, p.z, p.occ, p.nts, w0s, cpid);
+                O.template push<BOX>(d, home, nk_rank(mA), __popcll(mA), p.x, p.y, p.z, p.occ, p.nts, w0s, cpid);
                 if (ROUGH && away) {                       // one 64-byte record into the inbox of the segment that owns the new mode
                     const int dst = hseg;
                     const int at = atomicAdd(d.mig_n + dst, 1);
@@ -1087,7 +984,7 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
             }
             NK_STAMP(3);
         };
-        if (PF2) { for (int t = 0; t <= nA; t += 2) { turn(bA, t); if (t + 1 <= nA) turn(bB, t + 1); } drained(bA); drained(bB); }
+        if (SPLIT) { for (int t = 0; t <= nA; t += 2) { turn(bA, t); if (t + 1 <= nA) turn(bB, t + 1); } drained(bA); drained(bB); }
         else for (int t = 0; t <= nA; ++t) turn(bA, t);
 #ifdef NK_STAMPS
         if (lane == 0 && d.stamps) {
@@ -1104,7 +1001,6 @@ __device__ __forceinline__ void nk_sweep_body(const NkDev &d, NkLds L, uint32_t 
             w[0] = st_entry_r; w[1] = st_r0; w[2] = r1_;
         }
 #endif
-        if (O.on > 0) O.flush(d, base, lane, O.on);
         const int w = O.wout;
         if (SPLIT && lane == 0) d.seg_evq[seg] = qn < d.segcap ? qn : d.segcap;
         const int nlo = down ? hi - (w < count ? w : count) : wlo;                  // where the live particles begin now

@@ -298,11 +298,11 @@ class OracleSim(object):
     def __init__(self, mat, mesh, sv, res, rough, params, store, T_sv, box=False):
         """box: False = the reference's rule (events decided on the cached, decremented n_timesteps: what the goldens pin);
         'auto' = the engine's rule: on an axis-aligned box whose sides are its facets the hit is read off the position
-        (nk_oracle.h nko_params::box), unless NK_NO_BOX / NK_SPLIT / NK_LAYOUT=soa switch the engine's box store off."""
+        (nk_oracle.h nko_params::box), unless NK_NO_BOX / NK_SPLIT switch the engine's box store off."""
         self.L = lib()
         self.mat, self.mesh, self.sv, self.res, self.rough, self.p, self.P = mat, mesh, sv, res, rough, params, store
         self.p.box = 0
-        off = os.environ.get('NK_NO_BOX') or os.environ.get('NK_SPLIT') or os.environ.get('NK_LAYOUT') == 'soa'
+        off = os.environ.get('NK_NO_BOX') or os.environ.get('NK_SPLIT')
         if box and not off and self.L.nko_box_detect(C.byref(self.mesh), C.byref(self.p)):
             self.p.box = 1
         self.S = sv.S
