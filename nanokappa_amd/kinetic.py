@@ -153,9 +153,25 @@ def parallel_pair(src_facets, normals, areas, centroids):
     return L, A0, int(np.argmax(np.abs(n0)))
 
 
+def left_out(res):
+    """(overflow, message) of an Engine.kinetic_flights result or of kinetic_groups.pool(): how many terms lay above their bounds
+    and were left out of the integer sums (a call that leaves terms out still returns its results), and the engine's text."""
+    rep = res.get('report', {}) or {}
+    return int(rep.get('overflow', 0) or 0), str(rep.get('message', '') or '')
+
+
+def left_out_warning(s):
+    """The one line Population.kinetic_flights prints for a summarise() dict whose sums miss terms; None where none was left out."""
+    if int(s.get('overflow', 0)) <= 0:
+        return None
+    return 'Warning: kinetic flights: %d term(s) above their bounds were left out of the sums: %s' % (
+        int(s['overflow']), ' '.join(str(s.get('message', '')).split()) or 'the engine gave no text')
+
+
 def summarise(res, c, group_vel, tau, T, areas, normals_in, T_f, sv_volume, pair=None, omega_c=None, qv=None):
     """Everything one reads off an Engine.kinetic_flights result.  areas [F], normals_in [F, 3] of the sources; T_f [F] their
-    temperatures (T_ref = the mean); sv_volume [S]; pair: parallel_pair()'s (L, A, axis) or None.  With omega_c = C_m (eV / K, the
+    temperatures (T_ref = the mean); sv_volume [S]; pair: parallel_pair()'s (L, A, axis) or None.  `overflow` (int) and `message`
+    are left_out()'s: above 0, terms are missing from the sums and every figure below is short of them.  With omega_c = C_m (eV / K, the
     per-mode heat capacity of free_path) and qv also the bulk conductivity and the free-path estimate's closed form along the axis."""
     n = int(res['n'])
     lv = live_modes(c, tau)
@@ -172,7 +188,7 @@ def summarise(res, c, group_vel, tau, T, areas, normals_in, T_f, sv_volume, pair
                capped=np.asarray(res['capped'], dtype=np.int64), events=np.asarray(res['events'], dtype=np.int64),
                casts=np.asarray(res['casts'], dtype=np.int64), D=np.asarray(res['D']), D2=np.asarray(res['D2']),
                dwell_total=np.asarray(res['dwell_total']), dwell=np.asarray(res['dwell']), flux=np.asarray(res['flux']),
-               report=dict(res.get('report', {})), kappa_eff=np.nan, kappa_eff_se=np.nan, kappa_bulk=np.nan, kappa_free_path=np.nan,
+               report=dict(res.get('report', {})), overflow=left_out(res)[0], message=left_out(res)[1], kappa_eff=np.nan, kappa_eff_se=np.nan, kappa_bulk=np.nan, kappa_free_path=np.nan,
                L=np.nan, A=np.nan, axis=-1)
     if pair is not None:
         L, A, axis = pair

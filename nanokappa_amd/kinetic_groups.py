@@ -114,6 +114,7 @@ def pool(results):
     for k in ('rays', 'events', 'casts', 'lost', 'missed', 'capped', 'overflow', 'seconds', 'calls'):
         if k in rep:
             rep[k] = sum(r['report'][k] for r in results) if k != 'calls' else results[-1]['report'][k]
+    rep['message'] = '; '.join(m for m in (KN.left_out(r)[1] for r in results) if m)      # (every call that left terms out says so)
     out = dict(n=int(first['n']) * len(results), source_facet=np.asarray(first['source_facet']), ends=rows[:, :nf].copy(), lost=rows[:, 8].copy(),
                missed=rows[:, 9].copy(), capped=rows[:, 10].copy(), events=rows[:, 11].copy(), casts=rows[:, 12].copy(),
                D=rows[:, 13:16] * 2.0 ** -rep['k_D'], D2=rows[:, 16:19] * 2.0 ** -rep['k_D2'], dwell_total=rows[:, 19] * 2.0 ** -rep['k_T'],
@@ -202,7 +203,8 @@ def summarise_groups(res, c, group_vel, tau, areas, normals_in, T_f, sv_volume, 
                T_ref=float(T_f.mean()), grp=np.asarray(res['grp'], dtype=np.int64), dwell_g=np.asarray(res['dwell_g']),
                flux_g=np.asarray(res['flux_g']), batches=0 if batches is None else len(batches), L=np.nan, A=np.nan, axis=-1,
                kappa_g=np.full(G + 1, np.nan), kappa_flux=np.asarray(np.nan), accumulation=np.full(G, np.nan),
-               kappa_bulk_g=np.full(G + 1, np.nan), suppression=np.full(G + 1, np.nan))
+               kappa_bulk_g=np.full(G + 1, np.nan), suppression=np.full(G + 1, np.nan), overflow=KN.left_out(res)[0],
+               message=KN.left_out(res)[1])
     out.update(_quantities(res, g, T_f, V, c_g, pair, sign))
     if pair is not None:
         out.update(L=float(pair[0]), A=float(pair[1]), axis=int(pair[2]))

@@ -621,6 +621,9 @@ class Population(Constants):
         s = KN.summarise(res, c, ph.group_vel, tau, T, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,
                          geo.subvol_volume, pair=pair, omega_c=omega_c, qv=qv)
         self.kinetic_last = s
+        line = KN.left_out_warning(s)                # (one call or the pooled batches: the files below are written all the same)
+        if line:
+            print(line)
         sg = None
         if table is not None:
             sg = KG.summarise_groups(res, c, ph.group_vel, tau, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,

@@ -65,7 +65,7 @@ def restate_grouped(table, G, g, sv, group_vel, tau, c, n, seed=0, max_events=MA
     D, T = np.zeros((R, 3)), np.zeros(R)
     hsh = np.zeros(R, dtype=np.uint64)
     sub = np.zeros((F, S, 4), dtype=np.int64)
-    ovSt = ovSx = 0
+    ovSt, ovSx = np.zeros(F, dtype=np.int64), np.zeros(F, dtype=np.int64)       # the segments' terms left out, by source
     act = np.nonzero(mode >= 0)[0]
     while act.size:
         m = mode[act]
@@ -88,12 +88,12 @@ def restate_grouped(table, G, g, sv, group_vel, tau, c, n, seed=0, max_events=MA
         D[i] = fma(t[:, None], v, D[i])
         T[i] = T[i] + t
         s = K.classify(sv, K._pos(up * t, v, x[i], fused))
-        qt, o = K._q(t, st, bd['B_t'])
-        ovSt += o
+        qt, _ = K._q(t, st, bd['B_t'])
+        ovSt += K._over(t, bd['B_t'], sidx[i], F)
         q4 = [qt]
         for a in range(3):
-            qa, o = K._q(t * v[:, a], sx, bd['B_x'])
-            ovSx += o
+            qa, _ = K._q(t * v[:, a], sx, bd['B_x'])
+            ovSx += K._over(t * v[:, a], bd['B_x'], sidx[i], F)
             q4.append(qa)
         for w in range(4):
             np.add.at(sub[:, :, w], (sidx[i], s), q4[w])
@@ -156,7 +156,7 @@ def restate_grouped(table, G, g, sv, group_vel, tau, c, n, seed=0, max_events=MA
             rows[f, 16 + a], rows[f, 21] = q.sum(), rows[f, 21] + o
         q, o = K._q(T[r], sT, bd['BT'])
         rows[f, 19], rows[f, 22] = q.sum(), o
-    rows[0, 23], rows[0, 24] = ovSt, ovSx
+    rows[:, 23], rows[:, 24] = ovSt, ovSx
     sh = (F, n)
     rep = dict(bd, rays=R, events=int(k.sum()), casts=int(ncast.sum()), lost=int((end == END_LOST).sum()), missed=int((end == END_MISSED).sum()),
                capped=int((end == END_CAPPED).sum()), overflow=int(rows[:, 20:25].sum()), n_sources=F, n_subvolumes=S, source_facet=list(src))
