@@ -571,7 +571,8 @@ typedef struct {
 } nk_kinetic_args;
 typedef struct {                 /* any pointer may be NULL */
     int64_t *rows;               /* [n_sources * NK_KIN_ROW_WORDS] per source: ends[8], lost, missed, capped, events, casts, D[3] 2^k_D,
-                                  * D^2[3] 2^k_D2, dwell 2^k_T, then the terms left out: of D, D^2, the dwell, a segment's t, its t v */
+                                  * D^2[3] 2^k_D2, dwell 2^k_T, then the terms left out: of D, D^2, the dwell, a segment's t, its t v;
+                                  * word 25: the segment points clamped into the grid (nk_kinetic_flights_map only, 0 otherwise) */
     int64_t *sub;                /* [n_sources * S * 4] per (source, subvolume): dwell 2^k_t, t v_x, t v_y, t v_z 2^k_x */
 } nk_kinetic_out;
 typedef struct {                 /* per ray (ray = source index * n_samples + sample); any pointer may be NULL */
@@ -627,6 +628,32 @@ typedef struct {                 /* the pointer may be NULL */
  * Nothing is launched or allocated then. */
 int nk_kinetic_flights_groups(nk_ctx *ctx, const nk_kinetic_args *args, const nk_kinetic_groups *groups, const nk_kinetic_out *out,
                               const nk_kinetic_group_out *group_out, const nk_kinetic_rays *rays, nk_kinetic_report *report);
+
+/* Kinetic maps: nk_kinetic_flights with the segments' words also binned on a 3-D grid -- the steady temperature and heat-flux field
+ * of the structure.  The grid is the field's: cell of a point = floor((x_a - lo_a) * (1 / h_a)) per axis, an index outside [0, n_a)
+ * or a NaN clamped into the edge cell and counted; cell order (ix * ny + iy) * nz + iz.  Every segment that adds its four integers
+ * {t, t v_x, t v_y, t v_z} to the words of (source, subvolume of x_p) adds the SAME four integers to the line of (source, cell of
+ * x_p), x_p the same uniform point of the segment: no second rounding, no new bound, no new random number.  So for every source and
+ * word the cells add up to the subvolumes of `sub` bit for bit.  The lines go straight to memory; `sub` keeps its LDS bins.  The
+ * points clamped are counted per source in word 25 of the source's row (0 in a call of the two entries above).  Everything else --
+ * rows, sub, the per-ray outputs, the report -- is what nk_kinetic_flights returns for the same arguments; the three entries run
+ * through one host function. */
+#define NK_KIN_ROW_CLAMPED 25
+#define NK_KIN_MAX_MAP_CELLS (1 << 24)
+#define NK_KIN_MAX_MAP_WORDS (1 << 27)
+typedef struct {
+    int32_t n[3];                /* cells per axis, > 0; at most NK_KIN_MAX_MAP_CELLS in all */
+    int32_t pad_;
+    double lo[3], h[3];          /* the corner of cell (0, 0, 0) and the cell sizes (angstrom), h > 0 */
+} nk_kinetic_grid;
+typedef struct {                 /* the pointer may be NULL */
+    int64_t *cells;              /* [n_sources * ncells * 4] per (source, cell): dwell 2^k_t, t v_x, t v_y, t v_z 2^k_x */
+} nk_kinetic_map_out;
+/* NK_ERR_ARG as nk_kinetic_flights, and with a text that names the cause: grid NULL; n or h not positive or h not finite; lo not
+ * finite; more than NK_KIN_MAX_MAP_CELLS cells; n_sources * ncells * 4 above NK_KIN_MAX_MAP_WORDS.  Nothing is launched or
+ * allocated then and the report is all zero. */
+int nk_kinetic_flights_map(nk_ctx *ctx, const nk_kinetic_args *args, const nk_kinetic_grid *grid, const nk_kinetic_out *out,
+                           const nk_kinetic_map_out *map_out, const nk_kinetic_rays *rays, nk_kinetic_report *report);
 
 /* Replica groups: R contexts that hold the same problem under different seeds (the runs behind an error bar) are stepped by
  * shared launches -- per step ONE sweep and ONE tail launch for all of them instead of R of each, and one wait per call.  A

@@ -1,6 +1,6 @@
 """Parameter-file / command-line front end with the reference's flags and semantics
 (reference argument_parser.py:6-181): `--from_file <txt>` splits the file on whitespace and feeds argparse.
-Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep`, `--free_path_map`, `--kinetic` and `--kinetic_groups`."""
+Additions: `--seed` (the reference uses the unseeded global NumPy generator), `--device`, `--spectral_bands`, `--field_grid`, `--field_groups`, `--field_solid`, `--mode_tally`, `--free_path`, `--free_path_sweep`, `--free_path_map`, `--kinetic`, `--kinetic_groups` and `--kinetic_map`."""
 import argparse
 import os
 import sys
@@ -89,6 +89,12 @@ def initialise_parser(debug_flag=False):
            'temperature deviation and heat flux of every subvolume); kind = frequency (G bins), branch, mfp (G log-spaced bins of '
            'the mean free path of the call\'s lifetimes) or direction (G bins of the cosine between the group velocity and the '
            'axis x|y|z, default the transport axis); off by default')
+    a('--kinetic_map', default=[], type=str, nargs='*',
+      help='nx ny nz [cell|solid]: with --kinetic N, also bin every segment of the flights on the GPU into the cells of an nx x ny '
+           'x nz grid over the bounding box (the grid of --field_grid), in 8 batches of N / 8 rays whose spread gives the error '
+           'bars, and write kinetic_map.npz and kinetic_map.vtk -- the steady temperature T, its deviation dT and the heat flux q '
+           'of every cell with their standard errors; cell (the default) divides by the cell volume, solid by the exact solid '
+           'volume of every cell (and adds solid_fraction); off by default')
     a('--free_path_sweep', default=[], type=str, nargs='*',
       help='scale s1 s2 ... | temperature T1 T2 ...: with --free_path N, also weigh the same rays once per value (at most 32) -- '
            'the structure scaled by s with unchanged roughness, or the structure as it is at the temperature T (K) -- and write '

@@ -4230,9 +4230,11 @@ static int nk_kin_table(nk_ctx *ctx, const char *name, const double *t, int64_t 
     NK_ARG(M > 0 && t[M - 1] == 1.0, std::string("nk_kinetic_flights: ") + name + " does not end at 1 (no live mode?)");
     return NK_OK;
 }
-// Both entries: nk_kinetic_flights is this function without groups (g and gout null).
+// The three entries: nk_kinetic_flights is this function without groups (g and gout null) and without a map (is_map false; gr and
+// mout null); nk_kinetic_flights_map is it with the grid gr (never with groups).
 static int nk_kin_run(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_groups *g, const nk_kinetic_out *out,
-                      const nk_kinetic_group_out *gout, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
+                      const nk_kinetic_group_out *gout, const nk_kinetic_rays *pr, nk_kinetic_report *rep, bool is_map = false,
+                      const nk_kinetic_grid *gr = nullptr, const nk_kinetic_map_out *mout = nullptr) {
     if (rep) memset(rep, 0, sizeof(*rep));
     if (!ctx) return NK_ERR_ARG;                                // (no context to hold a text)
     NK_ARG(a, "nk_kinetic_flights: NULL argument");
@@ -4285,6 +4287,21 @@ static int nk_kin_run(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_gr
         NK_ARG(words <= NK_KIN_MAX_GROUP_WORDS, "nk_kinetic_flights_groups: " + std::to_string(r.n_sources) + " sources x " + std::to_string(d.S) +
                                                     " subvolumes x " + std::to_string(GC) + " columns x 4 = " + std::to_string((long long)words) +
                                                     " words are more than a call takes (2^24)");
+    }
+    // kinetic maps: the field's grid; the lines of (source, cell) live in memory for the length of the call
+    int64_t ncells = 0, nmap = 0;
+    if (is_map) {
+        NK_ARG(gr, "nk_kinetic_flights_map: grid is NULL (the cell counts n, the corner lo and the cell sizes h)");
+        NK_ARG(gr->n[0] > 0 && gr->n[1] > 0 && gr->n[2] > 0, "nk_kinetic_flights_map: the cell counts n must be positive");
+        for (int c = 0; c < 3; ++c) {
+            NK_ARG(gr->h[c] > 0.0 && std::isfinite(gr->h[c]), "nk_kinetic_flights_map: the cell sizes h must be positive and finite");
+            NK_ARG(std::isfinite(gr->lo[c]), "nk_kinetic_flights_map: the corner lo must be finite");
+        }
+        ncells = (int64_t)gr->n[0] * gr->n[1] * gr->n[2];
+        NK_ARG(ncells <= NK_KIN_MAX_MAP_CELLS, "nk_kinetic_flights_map: " + std::to_string((long long)ncells) + " cells are more than the grid takes (2^24)");
+        nmap = (int64_t)r.n_sources * ncells * 4;
+        NK_ARG(nmap <= NK_KIN_MAX_MAP_WORDS, "nk_kinetic_flights_map: " + std::to_string(r.n_sources) + " sources x " + std::to_string((long long)ncells) +
+                                                 " cells x 4 = " + std::to_string((long long)nmap) + " words are more than a call takes (2^27)");
     }
     // bounds and scales: a segment lasts min(t_s, t_c), t_s <= 38 tau (u >= 2^-54) and, cast from inside the mesh, t_c <= 2 diagonal / |v|
     double diag = 0.0;
@@ -4346,6 +4363,12 @@ static int nk_kin_run(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_gr
         dgrp.reset(new NkDevBuf<unsigned long long>(nullptr, ngrp)); NK_HIP(dgrp->err);
         f.group = dcol->p; f.GC = GC; f.grp = dgrp->p;
     }
+    std::unique_ptr<NkDevBuf<unsigned long long>> dmap;
+    if (is_map) {
+        dmap.reset(new NkDevBuf<unsigned long long>(nullptr, nmap)); NK_HIP(dmap->err);
+        for (int c = 0; c < 3; ++c) { f.gn[c] = gr->n[c]; f.lo[c] = gr->lo[c]; f.inv_h[c] = 1.0 / gr->h[c]; }
+        f.ncells = (int32_t)ncells; f.map = dmap->p;
+    }
     f.tau = dtau.p; f.vg = ctx->d_vg; f.cdf_scatter = dcs.p; f.cdf_flux = dcf.p;
     f.rows = drows.p; f.sub = dsub.p;
     f.ray_x0 = (w && pr->x0) ? rx.p : nullptr; f.ray_D = (w && pr->D) ? rD.p : nullptr; f.ray_T = (w && pr->dwell) ? rT.p : nullptr;
@@ -4354,10 +4377,11 @@ static int nk_kin_run(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_gr
     f.ray_hash = (w && pr->hash) ? rh.p : nullptr;
     r.bytes = M * 24 + ((int64_t)r.n_sources * NK_KIN_ROW + nsub) * 8 + (f.ray_x0 ? rays * 24 : 0) + (f.ray_D ? rays * 24 : 0) + (f.ray_T ? rays * 8 : 0) +
               (f.ray_mode ? rays * 4 : 0) + (f.ray_end ? rays * 4 : 0) + (f.ray_events ? rays * 4 : 0) + (f.ray_casts ? rays * 4 : 0) + (f.ray_hash ? rays * 8 : 0) +
-              (g ? M * 4 + ngrp * 8 : 0);
+              (g ? M * 4 + ngrp * 8 : 0) + nmap * 8;
     NK_HIP(hipMemsetAsync(drows.p, 0, (size_t)r.n_sources * NK_KIN_ROW * 8, ctx->stream));      // (outside the timed window)
     NK_HIP(hipMemsetAsync(dsub.p, 0, (size_t)std::max<int64_t>(nsub, 1) * 8, ctx->stream));
     if (g) NK_HIP(hipMemsetAsync(dgrp->p, 0, (size_t)std::max<int64_t>(ngrp, 1) * 8, ctx->stream));
+    if (is_map) NK_HIP(hipMemsetAsync(dmap->p, 0, (size_t)nmap * 8, ctx->stream));
     NK_HIP(nk_free_timed(ctx->stream, r.seconds, [&] { return nk_kinetic_launch(d, f, r.geometry_mode, lds, r.lds_bins != 0, ctx->stream); }));
     std::vector<unsigned long long> hrows((size_t)r.n_sources * NK_KIN_ROW);
     NK_HIP(drows.get(hrows.data(), (int64_t)hrows.size()));
@@ -4372,6 +4396,7 @@ static int nk_kin_run(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_gr
     if (out && out->rows) memcpy(out->rows, hrows.data(), hrows.size() * 8);
     if (out && out->sub) NK_HIP(hipMemcpy(out->sub, dsub.p, (size_t)nsub * 8, hipMemcpyDeviceToHost));
     if (g && gout && gout->grp) NK_HIP(hipMemcpy(gout->grp, dgrp->p, (size_t)ngrp * 8, hipMemcpyDeviceToHost));
+    if (is_map && mout && mout->cells) NK_HIP(hipMemcpy(mout->cells, dmap->p, (size_t)nmap * 8, hipMemcpyDeviceToHost));
     if (w) {
         NK_HIP(rx.get(pr->x0, rays * 3)); NK_HIP(rD.get(pr->D, rays * 3)); NK_HIP(rT.get(pr->dwell, rays));
         NK_HIP(rm.get(pr->mode, rays)); NK_HIP(re.get(pr->end, rays)); NK_HIP(rv.get(pr->events, rays)); NK_HIP(rc.get(pr->casts, rays));
@@ -4397,4 +4422,8 @@ int nk_kinetic_flights_groups(nk_ctx *ctx, const nk_kinetic_args *a, const nk_ki
         NK_ARG(g, "nk_kinetic_flights_groups: groups is NULL (n_groups and the group of every mode)");
     }
     return nk_kin_run(ctx, a, g, out, gout, pr, rep);
+}
+int nk_kinetic_flights_map(nk_ctx *ctx, const nk_kinetic_args *a, const nk_kinetic_grid *gr, const nk_kinetic_out *out,
+                           const nk_kinetic_map_out *mout, const nk_kinetic_rays *pr, nk_kinetic_report *rep) {
+    return nk_kin_run(ctx, a, nullptr, out, nullptr, pr, rep, true, gr, mout);
 }

@@ -1,5 +1,5 @@
-// nk_kinetic.h -- kinetic flights (nk_kinetic_flights, nk_kinetic_flights_groups): what the kernel k_kinetic<GEOM, BINS, GROUPED>
-// (nk_kinetic.hip, a translation unit of its own like nk_freepath.hip) is handed, and its launch.  The C entry points are in
+// nk_kinetic.h -- kinetic flights (nk_kinetic_flights, nk_kinetic_flights_groups, nk_kinetic_flights_map): what the kernel
+// k_kinetic<GEOM, BINS, GROUPED, MAP> (nk_kinetic.hip, a translation unit of its own like nk_freepath.hip) is handed, and its launch.  The C entry points are in
 // nk_engine.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,9 +22,10 @@ struct NkDev;
 #define NK_KIN_WAVES 4           // waves per workgroup (NK_WG / 64)
 #define NK_KIN_MAX_SOURCES_DEV 8 // NK_KIN_MAX_SOURCES of the public header
 // a source's row of 64-bit words: ends[8], lost, missed, capped, events, casts, D[3] 2^k_D, D^2[3] 2^k_D2, dwell 2^k_T, then the
-// terms left out above their bounds: of D, of D^2, of the dwell (per ray), of a segment's time and of its displacement (per segment)
+// terms left out above their bounds: of D, of D^2, of the dwell (per ray), of a segment's time and of its displacement (per segment),
+// then the segment points clamped into the map's edge cells (map calls only; 0 otherwise)
 enum { NK_KR_ENDS = 0, NK_KR_LOST = 8, NK_KR_MISSED = 9, NK_KR_CAPPED = 10, NK_KR_EVENTS = 11, NK_KR_CASTS = 12, NK_KR_D = 13,
-       NK_KR_D2 = 16, NK_KR_T = 19, NK_KR_OVD = 20, NK_KR_OVD2 = 21, NK_KR_OVT = 22, NK_KR_OVST = 23, NK_KR_OVSX = 24, NK_KIN_ROW = 32 };
+       NK_KR_D2 = 16, NK_KR_T = 19, NK_KR_OVD = 20, NK_KR_OVD2 = 21, NK_KR_OVT = 22, NK_KR_OVST = 23, NK_KR_OVSX = 24, NK_KR_CLAMPED = 25, NK_KIN_ROW = 32 };
 // a ray's end code: >= 0 the source index of the reservoir that absorbed it
 #define NK_KIN_LOST (-1)
 #define NK_KIN_MISSED (-2)
@@ -50,10 +51,15 @@ struct NkKinDev {
     const int32_t *group;                                 // [M] the column of every mode, 0 .. GC-1
     int32_t GC, pad_;                                     // columns: the call's groups and the rest column
     unsigned long long *grp;                              // [nsrc * S * GC * 4], zeroed by the host
+    // kinetic maps (MAP; map null otherwise): a segment's four words also go to the line of (source, cell of x_p) on the field's
+    // grid, cell = floor((x - lo) * inv_h) per axis, clamped; cell order (ix * ny + iy) * nz + iz
+    int32_t gn[3], ncells;
+    double lo[3], inv_h[3];
+    unsigned long long *map;                              // [nsrc * ncells * 4], zeroed by the host
 };
 
 // one wave per (source, block of rays_per_wave rays); geom = 1 (planes in LDS) or 2 (tables in global memory, tree walk); lds = what
 // nk_lds_setup of that geometry mode and kind 0 needs; bins: the per-subvolume words are gathered in LDS (f.bins_off, nsrc * S * 4
 // words behind lds, times GC where f.GC > 0) before they go to memory.  f.GC > 0 picks the GROUPED instantiations and launches
-// k_kinetic_fold behind them on the same stream
+// k_kinetic_fold behind them on the same stream; f.map != nullptr picks the MAP instantiations (never together with f.GC > 0)
 hipError_t nk_kinetic_launch(const NkDev &d, const NkKinDev &f, int geom, size_t lds, bool bins, hipStream_t stream);

@@ -1,12 +1,12 @@
 // nk_kinetic.hip -- kinetic flights: the deviational, time-step-free Monte Carlo of the steady linearised BTE in the relaxation-time
-// picture (nk_kinetic_flights, nk_kinetic_flights_groups): k_kinetic<GEOM, BINS, GROUPED>, k_kinetic_fold and their launch.  The C
-// entry points are in nk_engine.hip.
+// picture (nk_kinetic_flights, nk_kinetic_flights_groups, nk_kinetic_flights_map): k_kinetic<GEOM, BINS, GROUPED, MAP>, k_kinetic_fold
+// and their launch.  The C entry points are in nk_engine.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "../../include/nanokappa_hip.h"
 // Every non-template kernel of nk_kernels.h becomes a template here that nothing instantiates, so this file's object holds
-// the eight instantiations of k_kinetic, k_kinetic_fold and nothing else (the trick of nk_modes.hip).
+// the twelve instantiations of k_kinetic, k_kinetic_fold and nothing else (the trick of nk_modes.hip).
 #define NK_KERNEL_LINKAGE template <int NK_NOT_IN_THIS_TU = 0>
 #include "nk_kernels.h"
 #include "nk_kinetic.h"
@@ -29,6 +29,9 @@
 // power-of-two scale (a term above its bound is left out and counted): per source they are reduced over the wave by the butterfly
 // and added once per wave; the per-subvolume words go to LDS bins first (BINS) or straight to memory.  Integer adds commute, so a
 // result depends neither on the order of the rays nor on the launch grid.
+// The map (MAP; DESIGN.md "Kinetic maps"): the same x_p also goes through the field's cell rule, and the segment's four integers --
+// the same ones, no second rounding -- are added to the line of (source, cell(x_p)) in memory as well; points outside the grid
+// land in its edge cells and are counted per source (row word NK_KR_CLAMPED).
 
 // a mode for a packet that leaves a surface with inward normal n: flux-weighted, by rejection; false after NK_KIN_TRIALS refusals
 __device__ __forceinline__ bool nk_kin_emit(const NkKinDev &f, uint64_t rid, uint32_t k, double nx, double ny, double nz, int &mode) {
@@ -53,11 +56,21 @@ __device__ __forceinline__ long long nk_kin_q(double term, double s, double B, u
     return (long long)rint(term * s);
 }
 
+// nk_field.hip's nk_field_axis: the field's cell rule along one axis
+__device__ __forceinline__ int nk_kin_axis(double x, double lo, double inv_h, int n, bool &clamped) {
+#pragma clang fp contract(off)
+    const double f = floor((x - lo) * inv_h);
+    if (!(f >= 0.0)) { clamped = true; return 0; }                  // (also a NaN coordinate)
+    if (f >= (double)n) { clamped = true; return n - 1; }
+    return (int)f;
+}
+
 // the flat lane loop of one wave: the rays [blk * rays_per_wave, ..) of source src
 // GROUPED (kinetic groups): the lane keeps the column of its mode beside tau -- loaded where tau is, when the mode changes -- and a
 // segment's four words go to (source, subvolume, column) instead of (source, subvolume): the loop still does four adds per segment,
 // and `sub` is folded from the columns afterwards (k_kinetic_fold)
-template <int GEOM, bool BINS, bool GROUPED>
+// MAP (kinetic maps): the four words also go to the line of (source, cell of x_p) in memory -- four more adds per segment
+template <int GEOM, bool BINS, bool GROUPED, bool MAP>
 __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, const NkKinDev &f, int wi, int lane, unsigned long long *bins) {
 #pragma clang fp contract(off)
     const int src = wi / f.blocks, blk = wi - src * f.blocks;
@@ -72,6 +85,7 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
     if constexpr (GROUPED) sub = (BINS ? bins : f.grp) + (size_t)src * d.S * f.GC * 4;
     else if constexpr (BINS) sub = bins + (size_t)src * d.S * 4;
     else sub = f.sub + (size_t)src * d.S * 4;
+    [[maybe_unused]] unsigned int nClamped = 0u;             // MAP: segment points clamped into the grid's edge cells
     // the wave's sums
     unsigned int ends[NK_KIN_MAX_SOURCES_DEV];
 #pragma unroll
@@ -142,7 +156,8 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
                 Dx = __builtin_fma(t, vx, Dx); Dy = __builtin_fma(t, vy, Dy); Dz = __builtin_fma(t, vz, Dz);
                 T = T + t;
                 const double ap = up * t;
-                const int s = nk_classify(d, L.tb, __builtin_fma(ap, vx, x), __builtin_fma(ap, vy, y), __builtin_fma(ap, vz, z));
+                const double px = __builtin_fma(ap, vx, x), py = __builtin_fma(ap, vy, y), pz = __builtin_fma(ap, vz, z);
+                const int s = nk_classify(d, L.tb, px, py, pz);
                 unsigned long long *w;                      // s < S (and col < GC: the host checks the table)
                 if constexpr (GROUPED) w = sub + 4 * ((size_t)s * f.GC + col);
                 else w = sub + 4 * s;
@@ -152,6 +167,19 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
                 if (qx) atomicAdd(w + 1, (unsigned long long)qx);
                 if (qy) atomicAdd(w + 2, (unsigned long long)qy);
                 if (qz) atomicAdd(w + 3, (unsigned long long)qz);
+                if constexpr (MAP) {                        // the same integers into the line of (source, cell of x_p)
+                    bool cl = false;
+                    const int ix = nk_kin_axis(px, f.lo[0], f.inv_h[0], f.gn[0], cl);
+                    const int iy = nk_kin_axis(py, f.lo[1], f.inv_h[1], f.gn[1], cl);
+                    const int iz = nk_kin_axis(pz, f.lo[2], f.inv_h[2], f.gn[2], cl);
+                    nClamped += cl ? 1u : 0u;
+                    const int cell = (ix * f.gn[1] + iy) * f.gn[2] + iz;        // < ncells <= 2^24: every index is clamped
+                    unsigned long long *c = f.map + 4 * ((size_t)src * f.ncells + cell);
+                    if (qt) atomicAdd(c, (unsigned long long)qt);
+                    if (qx) atomicAdd(c + 1, (unsigned long long)qx);
+                    if (qy) atomicAdd(c + 2, (unsigned long long)qy);
+                    if (qz) atomicAdd(c + 3, (unsigned long long)qz);
+                }
                 ++k;
                 bool scatter_now = scat;
                 if (scat) {
@@ -229,10 +257,17 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
         const unsigned long long v = nk_fl_wave_sum(row[j]);
         if (lane == 0 && v) atomicAdd(out + j, v);
     }
+    if constexpr (MAP) {
+        const unsigned long long v = nk_fl_wave_sum((unsigned long long)nClamped);
+        if (lane == 0 && v) atomicAdd(out + NK_KR_CLAMPED, v);
+    }
 }
 
-template <int GEOM, bool BINS, bool GROUPED>
-__global__ __launch_bounds__(NK_WG) void k_kinetic(NkDev d, NkKinDev f) {
+// MAP asks for three waves per SIMD by name: left to itself the tree-walk instantiation with bins takes 170 VGPRs, two over what
+// three waves allow (168); asked, all four fit (141 / 137 / 164 / 160, nothing spilled).  The other eight get the default (1) and
+// compile to the instructions they had before the map existed.
+template <int GEOM, bool BINS, bool GROUPED, bool MAP>
+__global__ __launch_bounds__(NK_WG) __attribute__((amdgpu_waves_per_eu(MAP ? 3 : 1))) void k_kinetic(NkDev d, NkKinDev f) {
     extern __shared__ __align__(16) unsigned char smem[];
     NkLds L;
     nk_lds_setup<GEOM, 0>(d, smem, L);
@@ -244,7 +279,7 @@ __global__ __launch_bounds__(NK_WG) void k_kinetic(NkDev d, NkKinDev f) {
     }
     const int lane = (int)(threadIdx.x & 63u);
     const int wi = __builtin_amdgcn_readfirstlane((int)blockIdx.x * NK_KIN_WAVES + (int)(threadIdx.x >> 6));
-    if (wi < f.nsrc * f.blocks) nk_kin_wave<GEOM, BINS, GROUPED>(d, L, f, wi, lane, bins);
+    if (wi < f.nsrc * f.blocks) nk_kin_wave<GEOM, BINS, GROUPED, MAP>(d, L, f, wi, lane, bins);
     if constexpr (BINS) {
         __syncthreads();
         unsigned long long *out = GROUPED ? f.grp : f.sub;
@@ -266,30 +301,34 @@ __global__ __launch_bounds__(NK_WG) void k_kinetic_fold(NkKinDev f, int S) {
     f.sub[i] = v;
 }
 
-template <bool GROUPED>
+template <bool GROUPED, bool MAP>
 static void nk_kinetic_pick(const NkDev &d, const NkKinDev &f, int geom, size_t lds, bool bins, unsigned grid, hipStream_t stream) {
     if (bins) {
-        if (geom == 1) k_kinetic<1, true, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
-        else k_kinetic<2, true, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
+        if (geom == 1) k_kinetic<1, true, GROUPED, MAP><<<grid, NK_WG, lds, stream>>>(d, f);
+        else k_kinetic<2, true, GROUPED, MAP><<<grid, NK_WG, lds, stream>>>(d, f);
     } else {
-        if (geom == 1) k_kinetic<1, false, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
-        else k_kinetic<2, false, GROUPED><<<grid, NK_WG, lds, stream>>>(d, f);
+        if (geom == 1) k_kinetic<1, false, GROUPED, MAP><<<grid, NK_WG, lds, stream>>>(d, f);
+        else k_kinetic<2, false, GROUPED, MAP><<<grid, NK_WG, lds, stream>>>(d, f);
     }
 }
 
-// the dispatch of NK_GEOM_LAUNCH (nk_engine.hip): the geometry mode, the bins and the groups pick the instantiation
+// the dispatch of NK_GEOM_LAUNCH (nk_engine.hip): the geometry mode, the bins, the groups and the map pick the instantiation (the
+// host refuses groups together with a map: only GROUPED = false is instantiated with MAP = true)
 hipError_t nk_kinetic_launch(const NkDev &d, const NkKinDev &f, int geom, size_t lds, bool bins, hipStream_t stream) {
     const int waves = f.nsrc * f.blocks;
     if (waves <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((waves + NK_KIN_WAVES - 1) / NK_KIN_WAVES);
     if (f.GC > 0) {
-        nk_kinetic_pick<true>(d, f, geom, lds, bins, grid, stream);
+        if (f.map) return hipErrorInvalidValue;
+        nk_kinetic_pick<true, false>(d, f, geom, lds, bins, grid, stream);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         const int words = f.nsrc * d.S * 4;
         k_kinetic_fold<<<(unsigned)((words + NK_WG - 1) / NK_WG), NK_WG, 0, stream>>>(f, d.S);
+    } else if (f.map) {
+        nk_kinetic_pick<false, true>(d, f, geom, lds, bins, grid, stream);
     } else {
-        nk_kinetic_pick<false>(d, f, geom, lds, bins, grid, stream);
+        nk_kinetic_pick<false, false>(d, f, geom, lds, bins, grid, stream);
     }
     return hipGetLastError();
 }

@@ -93,7 +93,7 @@ EXPORTS = ['nk_device_count', 'nk_create', 'nk_destroy', 'nk_last_error', 'nk_se
            'nk_set_modes', 'nk_get_modes', 'nk_tally_modes_state', 'nk_modes_info',
            'nk_group_create', 'nk_group_destroy', 'nk_group_step', 'nk_group_info', 'nk_group_last_error',
            'nk_cell_solid_volume', 'nk_solid_last_error', 'nk_free_paths', 'nk_free_paths_info', 'nk_free_paths_columns',
-           'nk_free_paths_map', 'nk_free_paths_map_info', 'nk_kinetic_flights', 'nk_kinetic_flights_groups']
+           'nk_free_paths_map', 'nk_free_paths_map_info', 'nk_kinetic_flights', 'nk_kinetic_flights_groups', 'nk_kinetic_flights_map']
 
 class nk_field(C.Structure):
     _fields_ = [('lo', C.c_double * 3), ('h', C.c_double * 3), ('n', C.c_int32 * 3), ('every', C.c_int32), ('flags', C.c_int32),
@@ -178,6 +178,9 @@ KIN_MAX_SOURCES = 8          # NK_KIN_MAX_SOURCES (include/nanokappa_hip.h)
 KIN_ROW_WORDS = 32           # NK_KIN_ROW_WORDS
 KIN_MAX_GROUPS = 256         # NK_KIN_MAX_GROUPS
 KIN_MAX_GROUP_WORDS = 1 << 24  # NK_KIN_MAX_GROUP_WORDS
+KIN_ROW_CLAMPED = 25         # NK_KIN_ROW_CLAMPED
+KIN_MAX_MAP_CELLS = 1 << 24  # NK_KIN_MAX_MAP_CELLS
+KIN_MAX_MAP_WORDS = 1 << 27  # NK_KIN_MAX_MAP_WORDS
 
 
 class nk_kinetic_args(C.Structure):
@@ -195,6 +198,14 @@ class nk_kinetic_groups(C.Structure):
 
 class nk_kinetic_group_out(C.Structure):
     _fields_ = [('grp', C.POINTER(C.c_int64))]
+
+
+class nk_kinetic_grid(C.Structure):
+    _fields_ = [('n', C.c_int32 * 3), ('pad_', C.c_int32), ('lo', C.c_double * 3), ('h', C.c_double * 3)]
+
+
+class nk_kinetic_map_out(C.Structure):
+    _fields_ = [('cells', C.POINTER(C.c_int64))]
 
 
 class nk_kinetic_rays(C.Structure):
@@ -334,6 +345,9 @@ def _bind(L, optional):
     if 'nk_kinetic_flights_groups' not in optional or hasattr(L, 'nk_kinetic_flights_groups'):
         L.nk_kinetic_flights_groups.argtypes = [C.c_void_p, C.POINTER(nk_kinetic_args), C.POINTER(nk_kinetic_groups), C.POINTER(nk_kinetic_out),
                                                 C.POINTER(nk_kinetic_group_out), C.POINTER(nk_kinetic_rays), C.POINTER(nk_kinetic_report)]
+    if 'nk_kinetic_flights_map' not in optional or hasattr(L, 'nk_kinetic_flights_map'):
+        L.nk_kinetic_flights_map.argtypes = [C.c_void_p, C.POINTER(nk_kinetic_args), C.POINTER(nk_kinetic_grid), C.POINTER(nk_kinetic_out),
+                                             C.POINTER(nk_kinetic_map_out), C.POINTER(nk_kinetic_rays), C.POINTER(nk_kinetic_report)]
     return L
 
 
@@ -941,7 +955,7 @@ class Engine(object):
         return self._free_path_map_report(rep)
 
     # ------------------------------------------------------- kinetic flights
-    def kinetic_flights(self, tau, c, n=65536, max_events=0, seed=0, rays=False, rays_per_wave=0, lds_bins=True, groups=None):
+    def kinetic_flights(self, tau, c, n=65536, max_events=0, seed=0, rays=False, rays_per_wave=0, lds_bins=True, groups=None, grid=None):
         """Kinetic flights (nk_kinetic_flights; k_kinetic): n energy packets from every 'T' facet, flown, scattered (tau [Q*J], drawn
         in proportion to c / tau, c [Q*J] the volumetric heat capacity per mode), re-emitted by diffuse walls and absorbed by the
         reservoirs -- the steady linearised BTE in the relaxation-time picture (kinetic.py forms conductances and profiles).
@@ -955,8 +969,16 @@ class Engine(object):
         groups = (G, table): kinetic groups (nk_kinetic_flights_groups; kinetic_groups.py) -- table [Q*J] holds the group 0 .. G-1
         of every mode or -1; the result then also holds grp [F, S, G + 1, 4] (int64: sub's words per column, the last column for
         the modes with -1; the columns add up to sub bit for bit, and everything else is what the call without groups returns),
-        dwell_g [F, S, G + 1] and flux_g [F, S, G + 1, 3].  Without groups the dict and the entry called are the plain ones."""
+        dwell_g [F, S, G + 1] and flux_g [F, S, G + 1, 3].  Without groups the dict and the entry called are the plain ones.
+        grid = (lo, h, n_cells): kinetic maps (nk_kinetic_flights_map; kinetic_map.py) -- every segment's four integers also go to
+        the line of (source, cell of the segment's point) on the field's grid; the result then also holds map [F, nx, ny, nz, 4]
+        (int64; over the cells it adds up to sub over the subvolumes bit for bit), dwell_map [F, nx, ny, nz], flux_map [F, nx, ny,
+        nz, 3] and clamped [F] (points outside the grid, tallied in its edge cells; word 25 of rows); everything else is what the
+        call without grid returns.  grid together with groups is refused.  Without grid the dict and the entry called are today's."""
         from . import kinetic as KN
+        if grid is not None and groups is not None:
+            raise NkError('kinetic_flights: grid and groups were both given: a map per (cell, group) is not built; make one call with '
+                          'groups and one with grid under the same seed (rows and sub of the two are the same bits)')
         n = int(n)
         t, cc = _d(np.ravel(tau)), _d(np.ravel(c))
         if self.M > 0 and (t.shape[0] != self.M or cc.shape[0] != self.M):
@@ -983,7 +1005,25 @@ class Engine(object):
             pr.mode, pr.end, pr.events, pr.casts = (_p(ro[k], c_ip) for k in ('ray_mode', 'ray_end', 'ray_events', 'ray_casts'))
             pr.hash = _p(ro['ray_hash'], c_u64p)
         rep = nk_kinetic_report()
-        if groups is None:
+        if grid is not None:
+            # (the library refuses a bad grid by name; the buffer is sized here, so the counts are read with care)
+            glo, gh = _d(np.ravel(grid[0])), _d(np.ravel(grid[1]))
+            try:
+                nc = [int(k) for k in np.ravel(grid[2])]
+            except (TypeError, ValueError):
+                nc = []
+            if glo.shape[0] != 3 or gh.shape[0] != 3 or len(nc) != 3:
+                raise NkError('kinetic_flights: grid must be (lo [3], h [3], n_cells [3])')
+            gg, mo = nk_kinetic_grid(), nk_kinetic_map_out()
+            ok = min(nc) > 0 and max(nc) < (1 << 31) and nc[0] * nc[1] * nc[2] <= KIN_MAX_MAP_CELLS
+            gg.n[:] = [k if -(1 << 31) <= k < (1 << 31) else -1 for k in nc]
+            gg.lo[:], gg.h[:] = [float(x) for x in glo], [float(x) for x in gh]
+            ncells = nc[0] * nc[1] * nc[2] if ok else 0
+            cells = np.zeros(max(min(F * ncells * 4, KIN_MAX_MAP_WORDS), 1), dtype=np.int64)        # (a call never returns more words)
+            mo.cells = cells.ctypes.data_as(C.POINTER(C.c_int64))
+            rc = self.L.nk_kinetic_flights_map(self.h, C.byref(a), C.byref(gg), C.byref(o), C.byref(mo), C.byref(pr) if pr else None,
+                                               C.byref(rep))
+        elif groups is None:
             rc = self.L.nk_kinetic_flights(self.h, C.byref(a), C.byref(o), C.byref(pr) if pr else None, C.byref(rep))
         else:
             # (the library refuses a bad G or table by name; only the table's length is checked here, since it reads M entries)
@@ -1002,7 +1042,7 @@ class Engine(object):
                                                   C.byref(rep))
         r = {k: (list(getattr(rep, k)) if k == 'source_facet' else getattr(rep, k)) for k, _ in nk_kinetic_report._fields_ if k != 'pad_'}
         if rc != 0 and not (rc == ERR_CAPACITY and r['overflow'] > 0):
-            self._ck(rc, 'nk_kinetic_flights' if groups is None else 'nk_kinetic_flights_groups')
+            self._ck(rc, 'nk_kinetic_flights_map' if grid is not None else 'nk_kinetic_flights' if groups is None else 'nk_kinetic_flights_groups')
         nf = int(rep.n_sources)
         r['source_facet'] = r['source_facet'][:nf]
         r['message'] = self.L.nk_last_error(self.h).decode() if rc != 0 else ''
@@ -1015,6 +1055,10 @@ class Engine(object):
         if groups is not None:
             grp = grp[:nf * S * GC * 4].reshape(nf, S, GC, 4).copy()
             out.update(grp=grp, dwell_g=grp[..., 0] * 2.0 ** -r['k_t'], flux_g=grp[..., 1:4] * 2.0 ** -r['k_x'])
+        if grid is not None:
+            m = cells[:nf * ncells * 4].reshape((nf,) + tuple(nc) + (4,)).copy()
+            out.update(map=m, dwell_map=m[..., 0] * 2.0 ** -r['k_t'], flux_map=m[..., 1:4] * 2.0 ** -r['k_x'],
+                       clamped=rows[:, KIN_ROW_CLAMPED].copy())
         for k, v in ro.items():
             out[k] = v[:nf].copy()
         return out

@@ -49,6 +49,8 @@ def main(argv=None):
     kn_n, kn_T, kn_events = kinetic_option(getattr(args, 'kinetic', None))
     from .kinetic_groups import kinetic_groups_option, BATCHES_DEFAULT
     kg_G, kg_kind, kg_axis = kinetic_groups_option(getattr(args, 'kinetic_groups', None), kn_n)
+    from .kinetic_map import kinetic_map_option
+    km_n, km_volume = kinetic_map_option(getattr(args, 'kinetic_map', None), kn_n)
     args = generate_results_folder(args)
     out = None
     # nanokappa.py:34-36 compares the parsed value with 'file'; an explicit `--output file` arrives as the list ['file'] and
@@ -85,8 +87,13 @@ def main(argv=None):
         print('Kinetic flights: %d rays per reservoir...' % kn_n)
         if kg_G > 0:                           # --kinetic_groups G kind [axis]: the same flights in batches, tallied by group
             kn = pop.kinetic_flights(n=kn_n, T=kn_T, max_events=kn_events, groups=(kg_G, kg_kind, kg_axis), batches=BATCHES_DEFAULT)
-        else:
+        elif km_n is None:
             kn = pop.kinetic_flights(n=kn_n, T=kn_T, max_events=kn_events)
+        km = None
+        if km_n is not None:                   # --kinetic_map nx ny nz [cell|solid]: the same batches under the same seeds, binned by cell
+            km = pop.kinetic_map(km_n, n=kn_n, T=kn_T, max_events=kn_events, batches=BATCHES_DEFAULT, volume=km_volume, kinetic_files=kg_G <= 0)
+            if kg_G <= 0:                      # (with groups the grouped flights wrote k_kinetic.txt: rows and sub are the same bits)
+                kn = km['summary'] if km is not None else None
         if kn is not None:
             print('  T = %.2f K: %d sources, %d events, %d casts; %d lost, %d missed, %d cut off' %
                   (kn['T'], len(kn['g']), kn['events'].sum(), kn['casts'].sum(), kn['lost'].sum(), kn['missed'].sum(), kn['capped'].sum()))
@@ -98,6 +105,11 @@ def main(argv=None):
                 print('  %d %s groups in %d batches: kappa from the heat flux = %.4f +- %.4f W/m K; per group %s' %
                       (kg['G'], kg_kind, kg['batches'], float(kg['kappa_flux']), float(kg['kappa_flux_se']),
                        ' '.join('%.4f' % x for x in kg['kappa_g'][:kg['G']])))
+            if km is not None:
+                se = km['T_se'][np.isfinite(km['T_se'])]
+                print('  map of %d x %d x %d cells (%s volume) in %d batches: T from %.3f to %.3f K, largest standard error %.4f K; %d points clamped' %
+                      (km['n'] + (km['volume'], km['batches'], np.nanmin(km['T']), np.nanmax(km['T']), se.max() if se.size else np.nan,
+                                  int(km['clamped'].sum()))))
     if fp_n > 0:                               # --free_path N [T] [max_segments]: after the set-up, before the first step
         print('Free-path sampling: %d rays per mode...' % fp_n)
         fp = pop.free_paths(n=fp_n, T=fp_T, max_segments=fp_segments)

@@ -29,6 +29,7 @@ from . import free_sweep as FS
 from . import free_map as FM
 from . import kinetic as KN
 from . import kinetic_groups as KG
+from . import kinetic_map as KM
 from .engine import Engine
 from .sharding import shard_range
 
@@ -637,6 +638,62 @@ class Population(Constants):
                 KG.write_k_kinetic_groups(KG.k_kinetic_groups_path(self.results_folder_name), sg)
                 KG.write_kinetic_groups_npz(KG.kinetic_groups_npz_path(self.results_folder_name), sg)
         return s
+
+    def kinetic_map(self, n_cells, n=KN.N_DEFAULT, T=None, tau=None, max_events=KN.MAX_EVENTS_DEFAULT, seed=0, batches=KM.BATCHES_DEFAULT,
+                    volume='cell', write=True, kinetic_files=False):
+        """The steady temperature and heat-flux field of the structure from the linearised BTE: the kinetic flights of
+        kinetic_flights with every segment also binned on the GPU (Engine.kinetic_flights(grid=)) into the cells of the grid
+        field.grid_from_bounds(geometry.bounds, n_cells).  batches = B engine calls of ceil(n / B) rays per source under the seeds
+        of kinetic_flights(batches=B) -- seed, seed + 1, .. (seed 0: the run's) --, pooled by adding their integers; the spread
+        over the batches gives the standard error of every cell quantity (NaN for B = 1).  volume 'cell' divides by h_x h_y h_z,
+        'solid' by the exact solid volume of every cell (engine.cell_solid_volume, called once), which also gives
+        solid_fraction.  Returns kinetic_map.summarise_map()'s dict (T, dT, q per cell with their standard errors, the raw map,
+        the points clamped) with `summary`, kinetic.summarise() of the pooled flights (also kept as kinetic_last), and with a
+        results folder writes kinetic_map.npz and kinetic_map.vtk -- and, with kinetic_files, k_kinetic.txt and kinetic.npz of the
+        pooled flights.  Particles and step counter are not touched.  With several ranks rank 0 computes and writes; the others
+        return None."""
+        if self.rank != 0:
+            return None
+        ph, geo = self._ph, self._geo
+        if volume not in KM.VOLUMES:
+            raise ValueError("kinetic_map: volume must be 'cell' or 'solid', got %r" % (volume,))
+        B = int(batches)
+        if B < 1:
+            raise ValueError('kinetic_map: batches = %d must be at least 1' % B)
+        T = self._mean_reservoir_T() if T is None else float(T)
+        tau = FP.lifetimes(ph, T) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
+        qv = ph.number_of_qpoints * ph.volume_unitcell
+        c = KN.heat_capacity(ph.omega, T, qv, self.hbar, self.kb)
+        src = KN.source_facets(geo.bound_cond)
+        pair = KN.parallel_pair(src, geo.facets_normal, geo.facets_area, geo.facet_centroid)
+        lo, h, nc = FD.grid_from_bounds(geo.bounds, n_cells)
+        nb = -(-int(n) // B)
+        seeds = [int(seed)] if B == 1 else [(int(seed) or self.seed) + b for b in range(B)]
+        per = [self.engine.kinetic_flights(tau, c, n=nb, max_events=int(max_events), seed=s_, grid=(lo, h, nc)) for s_ in seeds]
+        res = per[0] if B == 1 else KM.pool(per)
+        T_f = np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src])
+        areas, normals_in = np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src]
+        s = KN.summarise(res, c, ph.group_vel, tau, T, areas, normals_in, T_f, geo.subvol_volume, pair=pair,
+                         omega_c=FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb), qv=qv)
+        self.kinetic_last = s
+        line = KN.left_out_warning(s)
+        if line:
+            print(line)
+        V = None
+        if volume == 'solid':
+            from .engine import cell_solid_volume
+            V = cell_solid_volume(geo.mesh.vertices, geo.mesh.faces, lo, h, nc, device=int(getattr(self.args, 'device', [0])[0]))
+        m = KM.summarise_map(res, c, ph.group_vel, tau, areas, normals_in, T_f, lo, h, nc, volume=volume, solid_volume=V,
+                             batches=per if B > 1 else None)
+        m.update(T_flights=T, summary=s)
+        self.kinetic_map_last = m
+        if write and self.results_folder_name:
+            KM.write_kinetic_map_npz(KM.kinetic_map_npz_path(self.results_folder_name), m)
+            KM.write_kinetic_map_vtk(KM.kinetic_map_vtk_path(self.results_folder_name), m, title=KM.vtk_title(m, T))
+            if kinetic_files:
+                KN.write_k_kinetic(KN.k_kinetic_path(self.results_folder_name), s)
+                KN.write_kinetic_npz(KN.kinetic_npz_path(self.results_folder_name), s)
+        return m
 
     def free_path_sweep(self, kind, values, n=FP.N_DEFAULT, T=None, modes=None, max_segments=FP.MAX_SEGMENTS_DEFAULT, w_min=FP.W_MIN_DEFAULT,
                         x0=None, seed=0, axis=None, write=True):

@@ -23,11 +23,11 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from free_sweep_speed import engine_c2, engine_wire72, spread  # noqa: E402
 
 
-def other_engine(case, path):
-    """The case's engine on another build of the library (engine.load_library(path); the grouped entry may be missing there: only
-    the plain call is made on it).  The set-up is engine_c2's / engine_wire72's with that engine."""
+def other_engine(case, path, optional=('nk_kinetic_flights_groups', 'nk_kinetic_flights_map')):
+    """The case's engine on another build of the library (engine.load_library(path); the entries named in `optional` may be missing
+    there: only the plain call is made on it).  The set-up is engine_c2's / engine_wire72's with that engine."""
     from nanokappa_amd.engine import Engine, load_library
-    lib = load_library(path, optional=('nk_kinetic_flights_groups',))
+    lib = load_library(path, optional=optional)
     if case == 'c2':
         import bench
         from nanokappa_amd import synthetic
