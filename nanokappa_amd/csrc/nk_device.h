@@ -519,6 +519,15 @@ __device__ __forceinline__ int nk_classify(const NkDev &d, const NkSvTab &tb, do
     }
     return best;
 }
+// the field's cell rule along one axis (the field maps, the free-path maps and the kinetic maps): floor((x - lo) * (1 / h)), an
+// index outside [0, n) clamped into the edge cell and flagged
+__device__ __forceinline__ int nk_field_axis(double x, double lo, double inv_h, int n, bool &clamped) {
+#pragma clang fp contract(off)
+    const double f = floor((x - lo) * inv_h);
+    if (!(f >= 0.0)) { clamped = true; return 0; }                  // (also a NaN coordinate)
+    if (f >= (double)n) { clamped = true; return n - 1; }
+    return (int)f;
+}
 // per-particle temperature, Population.py:570-571, :694-702; also returns 1 / T (from the table where T is a subvolume's)
 // RBF = false compiles the radial-basis branch out (the sweep is instantiated with and without it: inlined it costs
 // registers in every configuration, and it is a rarely used mode).

@@ -66,12 +66,6 @@ struct NkFieldDev {
     int32_t G;
 };
 #define NK_FIELD_WG 1024
-__device__ __forceinline__ int nk_field_axis(double x, double lo, double inv_h, int n, bool &clamped) {
-    const double f = floor((x - lo) * inv_h);
-    if (!(f >= 0.0)) { clamped = true; return 0; }                  // (also a NaN coordinate)
-    if (f >= (double)n) { clamped = true; return n - 1; }
-    return (int)f;
-}
 template <bool STATE, bool GROUPED>
 __global__ __launch_bounds__(NK_FIELD_WG) void k_field(NkDev d, NkFieldDev f) {
     extern __shared__ __align__(16) unsigned char smem[];

@@ -42,15 +42,6 @@
 // term above its bound (B_K, B_P, B_T) is left out and counted in the header line; the host reports it.  The rows and the per-ray
 // outputs of a map call are the plain call's bit for bit: the same statements.
 
-// nk_field.hip's nk_field_axis: the field's cell rule along one axis
-__device__ __forceinline__ int nk_fm_axis(double x, double lo, double inv_h, int n, bool &clamped) {
-#pragma clang fp contract(off)
-    const double f = floor((x - lo) * inv_h);
-    if (!(f >= 0.0)) { clamped = true; return 0; }                  // (also a NaN coordinate)
-    if (f >= (double)n) { clamped = true; return n - 1; }
-    return (int)f;
-}
-
 // one term into one word: rint(term s) as a two's-complement integer; above the bound (or a NaN) it is left out and counted
 __device__ __forceinline__ void nk_fm_add(unsigned long long *w, double term, double s, double B, unsigned int &over) {
 #pragma clang fp contract(off)
@@ -115,9 +106,9 @@ __global__ __launch_bounds__(NK_WG) void k_free_paths(NkDev d, NkFreeDev f, NkFr
         int cell = 0;
         if constexpr (MAP) {
             bool cl = false;
-            const int ix = nk_fm_axis(x, g.lo[0], g.inv_h[0], g.n[0], cl);
-            const int iy = nk_fm_axis(y, g.lo[1], g.inv_h[1], g.n[1], cl);
-            const int iz = nk_fm_axis(z, g.lo[2], g.inv_h[2], g.n[2], cl);
+            const int ix = nk_field_axis(x, g.lo[0], g.inv_h[0], g.n[0], cl);
+            const int iy = nk_field_axis(y, g.lo[1], g.inv_h[1], g.n[1], cl);
+            const int iz = nk_field_axis(z, g.lo[2], g.inv_h[2], g.n[2], cl);
             nClamped += cl ? 1u : 0u;
             cell = (ix * g.n[1] + iy) * g.n[2] + iz;
         }

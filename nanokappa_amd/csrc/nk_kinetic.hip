@@ -56,15 +56,6 @@ __device__ __forceinline__ long long nk_kin_q(double term, double s, double B, u
     return (long long)rint(term * s);
 }
 
-// nk_field.hip's nk_field_axis: the field's cell rule along one axis
-__device__ __forceinline__ int nk_kin_axis(double x, double lo, double inv_h, int n, bool &clamped) {
-#pragma clang fp contract(off)
-    const double f = floor((x - lo) * inv_h);
-    if (!(f >= 0.0)) { clamped = true; return 0; }                  // (also a NaN coordinate)
-    if (f >= (double)n) { clamped = true; return n - 1; }
-    return (int)f;
-}
-
 // the flat lane loop of one wave: the rays [blk * rays_per_wave, ..) of source src
 // GROUPED (kinetic groups): the lane keeps the column of its mode beside tau -- loaded where tau is, when the mode changes -- and a
 // segment's four words go to (source, subvolume, column) instead of (source, subvolume): the loop still does four adds per segment,
@@ -169,9 +160,9 @@ __device__ __forceinline__ void nk_kin_wave(const NkDev &d, const NkLds &L, cons
                 if (qz) atomicAdd(w + 3, (unsigned long long)qz);
                 if constexpr (MAP) {                        // the same integers into the line of (source, cell of x_p)
                     bool cl = false;
-                    const int ix = nk_kin_axis(px, f.lo[0], f.inv_h[0], f.gn[0], cl);
-                    const int iy = nk_kin_axis(py, f.lo[1], f.inv_h[1], f.gn[1], cl);
-                    const int iz = nk_kin_axis(pz, f.lo[2], f.inv_h[2], f.gn[2], cl);
+                    const int ix = nk_field_axis(px, f.lo[0], f.inv_h[0], f.gn[0], cl);
+                    const int iy = nk_field_axis(py, f.lo[1], f.inv_h[1], f.gn[1], cl);
+                    const int iz = nk_field_axis(pz, f.lo[2], f.inv_h[2], f.gn[2], cl);
                     nClamped += cl ? 1u : 0u;
                     const int cell = (ix * f.gn[1] + iy) * f.gn[2] + iz;        // < ncells <= 2^24: every index is clamped
                     unsigned long long *c = f.map + 4 * ((size_t)src * f.ncells + cell);

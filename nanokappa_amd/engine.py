@@ -1047,18 +1047,10 @@ class Engine(object):
         r['source_facet'] = r['source_facet'][:nf]
         r['message'] = self.L.nk_last_error(self.h).decode() if rc != 0 else ''
         rows, sub = rows[:nf].copy(), sub[:nf * S * 4].reshape(nf, S, 4).copy()
-        out = dict(n=n, source_facet=np.array(r['source_facet'], dtype=np.int32), ends=rows[:, :nf].copy(), lost=rows[:, 8].copy(),
-                   missed=rows[:, 9].copy(), capped=rows[:, 10].copy(), events=rows[:, 11].copy(), casts=rows[:, 12].copy(),
-                   D=rows[:, 13:16] * 2.0 ** -r['k_D'], D2=rows[:, 16:19] * 2.0 ** -r['k_D2'], dwell_total=rows[:, 19] * 2.0 ** -r['k_T'],
-                   dwell=sub[:, :, 0] * 2.0 ** -r['k_t'], flux=sub[:, :, 1:4] * 2.0 ** -r['k_x'], rows=rows, sub=sub,
+        grp = None if groups is None else grp[:nf * S * GC * 4].reshape(nf, S, GC, 4).copy()
+        m = None if grid is None else cells[:nf * ncells * 4].reshape((nf,) + tuple(nc) + (4,)).copy()
+        out = dict(n=n, source_facet=np.array(r['source_facet'], dtype=np.int32), **KN.derived(rows, sub, r, grp=grp, map=m),
                    cdf_scatter=cs, cdf_flux=cf, report=r)
-        if groups is not None:
-            grp = grp[:nf * S * GC * 4].reshape(nf, S, GC, 4).copy()
-            out.update(grp=grp, dwell_g=grp[..., 0] * 2.0 ** -r['k_t'], flux_g=grp[..., 1:4] * 2.0 ** -r['k_x'])
-        if grid is not None:
-            m = cells[:nf * ncells * 4].reshape((nf,) + tuple(nc) + (4,)).copy()
-            out.update(map=m, dwell_map=m[..., 0] * 2.0 ** -r['k_t'], flux_map=m[..., 1:4] * 2.0 ** -r['k_x'],
-                       clamped=rows[:, KIN_ROW_CLAMPED].copy())
         for k, v in ro.items():
             out[k] = v[:nf].copy()
         return out

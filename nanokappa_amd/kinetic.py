@@ -21,6 +21,7 @@ import numpy as np
 
 from . import free_path as FP
 from .constants import Constants
+from .engine import KIN_ROW_CLAMPED
 
 N_DEFAULT = 65536
 MAX_EVENTS_DEFAULT = 2 ** 20
@@ -151,6 +152,25 @@ def parallel_pair(src_facets, normals, areas, centroids):
     if not L > 0:
         return None
     return L, A0, int(np.argmax(np.abs(n0)))
+
+
+def derived(rows, sub, report, grp=None, map=None):
+    """What a result holds besides n, the sources and the tables, from its integers rows [F, 32], sub [F, S, 4] (int64) and the
+    report's scales k_*: the counts ends, lost, missed, capped, events, casts, the reals D, D2, dwell_total, dwell, flux (an integer
+    times 2^-k: exact), and rows and sub themselves; with grp [F, S, G + 1, 4] also grp, dwell_g, flux_g; with map [F, nx, ny, nz,
+    4] also map, dwell_map, flux_map and clamped.  Engine.kinetic_flights forms one call's result with it, kinetic_groups.pool and
+    kinetic_map.pool the pooled one."""
+    nf = rows.shape[0]
+    st, sx = 2.0 ** -report['k_t'], 2.0 ** -report['k_x']
+    out = dict(ends=rows[:, :nf].copy(), lost=rows[:, 8].copy(), missed=rows[:, 9].copy(), capped=rows[:, 10].copy(),
+               events=rows[:, 11].copy(), casts=rows[:, 12].copy(), D=rows[:, 13:16] * 2.0 ** -report['k_D'],
+               D2=rows[:, 16:19] * 2.0 ** -report['k_D2'], dwell_total=rows[:, 19] * 2.0 ** -report['k_T'], dwell=sub[:, :, 0] * st,
+               flux=sub[:, :, 1:4] * sx, rows=rows, sub=sub)
+    if grp is not None:
+        out.update(grp=grp, dwell_g=grp[..., 0] * st, flux_g=grp[..., 1:4] * sx)
+    if map is not None:
+        out.update(map=map, dwell_map=map[..., 0] * st, flux_map=map[..., 1:4] * sx, clamped=rows[:, KIN_ROW_CLAMPED].copy())
+    return out
 
 
 def left_out(res):

@@ -110,20 +110,13 @@ def pool(results):
             raise ValueError('kinetic_groups.pool: the calls differ in n')
     rows = sum(np.asarray(r['rows'], dtype=np.int64) for r in results)
     sub = sum(np.asarray(r['sub'], dtype=np.int64) for r in results)
-    nf = rows.shape[0]
+    grp = sum(np.asarray(r['grp'], dtype=np.int64) for r in results) if 'grp' in first else None
     for k in ('rays', 'events', 'casts', 'lost', 'missed', 'capped', 'overflow', 'seconds', 'calls'):
         if k in rep:
             rep[k] = sum(r['report'][k] for r in results) if k != 'calls' else results[-1]['report'][k]
     rep['message'] = '; '.join(m for m in (KN.left_out(r)[1] for r in results) if m)      # (every call that left terms out says so)
-    out = dict(n=int(first['n']) * len(results), source_facet=np.asarray(first['source_facet']), ends=rows[:, :nf].copy(), lost=rows[:, 8].copy(),
-               missed=rows[:, 9].copy(), capped=rows[:, 10].copy(), events=rows[:, 11].copy(), casts=rows[:, 12].copy(),
-               D=rows[:, 13:16] * 2.0 ** -rep['k_D'], D2=rows[:, 16:19] * 2.0 ** -rep['k_D2'], dwell_total=rows[:, 19] * 2.0 ** -rep['k_T'],
-               dwell=sub[:, :, 0] * 2.0 ** -rep['k_t'], flux=sub[:, :, 1:4] * 2.0 ** -rep['k_x'], rows=rows, sub=sub,
-               cdf_scatter=first['cdf_scatter'], cdf_flux=first['cdf_flux'], report=rep, batches=len(results))
-    if 'grp' in first:
-        grp = sum(np.asarray(r['grp'], dtype=np.int64) for r in results)
-        out.update(grp=grp, dwell_g=grp[..., 0] * 2.0 ** -rep['k_t'], flux_g=grp[..., 1:4] * 2.0 ** -rep['k_x'])
-    return out
+    return dict(n=int(first['n']) * len(results), source_facet=np.asarray(first['source_facet']), **KN.derived(rows, sub, rep, grp=grp),
+                cdf_scatter=first['cdf_scatter'], cdf_flux=first['cdf_flux'], report=rep, batches=len(results))
 
 
 def mean_se(a):

@@ -61,9 +61,7 @@ def pool(results):
             if np.shape(r['map']) != np.shape(first['map']):
                 raise ValueError('kinetic_map.pool: the calls differ in their grid')
         m = sum(np.asarray(r['map'], dtype=np.int64) for r in results)
-        rep = out['report']
-        out.update(map=m, dwell_map=m[..., 0] * 2.0 ** -rep['k_t'], flux_map=m[..., 1:4] * 2.0 ** -rep['k_x'],
-                   clamped=sum(np.asarray(r['clamped'], dtype=np.int64) for r in results))
+        out.update(KN.derived(out['rows'], out['sub'], out['report'], map=m))
     return out
 
 

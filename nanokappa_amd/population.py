@@ -571,6 +571,40 @@ class Population(Constants):
             FP.write_free_path_npz(FP.free_path_npz_path(self.results_folder_name), s)
         return s
 
+    def _kinetic_inputs(self, T, tau):
+        """What kinetic_flights and kinetic_map fly and summarise with, as a dict: T (default: the mean reservoir temperature), tau
+        [Q*J] (default: Phonon.lifetime_function at T), the heat capacities c at T and qv, the sources `src` with their temperatures
+        T_f, `areas` and inward normals `normals_in`, `pair` (kinetic.parallel_pair) and omega_c (free_path's per-mode C_m)."""
+        ph, geo = self._ph, self._geo
+        T = self._mean_reservoir_T() if T is None else float(T)
+        tau = FP.lifetimes(ph, T) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
+        qv = ph.number_of_qpoints * ph.volume_unitcell
+        src = KN.source_facets(geo.bound_cond)
+        return dict(T=T, tau=tau, c=KN.heat_capacity(ph.omega, T, qv, self.hbar, self.kb), qv=qv, src=src,
+                    pair=KN.parallel_pair(src, geo.facets_normal, geo.facets_area, geo.facet_centroid),
+                    T_f=np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src]),
+                    areas=np.asarray(geo.facets_area)[src], normals_in=-np.asarray(geo.facets_normal)[src],
+                    omega_c=FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb))
+
+    def _kinetic_batches(self, k, n, B, max_events, seed, pool, **tally):
+        """(the B results, their pool): B engine calls of ceil(n / B) rays per source with _kinetic_inputs' k and the tally's
+        argument (groups= or grid=).  One call: the caller's seed as it is (0 = the engine's own, which is the run's).  Batches need
+        B different, known seeds: seed, seed + 1, ..; for seed 0 they start at the run's seed, the one the engine would have used."""
+        nb = -(-int(n) // B)
+        seeds = [int(seed)] if B == 1 else [(int(seed) or self.seed) + b for b in range(B)]
+        per = [self.engine.kinetic_flights(k['tau'], k['c'], n=nb, max_events=int(max_events), seed=s_, **tally) for s_ in seeds]
+        return per, per[0] if B == 1 else pool(per)
+
+    def _kinetic_summary(self, res, k):
+        """kinetic.summarise() of a result (or a pool) with _kinetic_inputs' k: kept as kinetic_last, its left-out warning printed."""
+        s = KN.summarise(res, k['c'], self._ph.group_vel, k['tau'], k['T'], k['areas'], k['normals_in'], k['T_f'], self._geo.subvol_volume,
+                         pair=k['pair'], omega_c=k['omega_c'], qv=k['qv'])
+        self.kinetic_last = s
+        line = KN.left_out_warning(s)
+        if line:
+            print(line)
+        return s
+
     def kinetic_flights(self, n=KN.N_DEFAULT, T=None, tau=None, max_events=KN.MAX_EVENTS_DEFAULT, seed=0, write=True, groups=None, batches=1):
         """Conductance between the reservoirs and the temperature and heat-flux profile of the steady linearised BTE, by kinetic
         flights on the GPU (Engine.kinetic_flights): n energy packets from every 'T' facet with the lifetimes `tau` [Q*J]
@@ -589,12 +623,8 @@ class Population(Constants):
         if self.rank != 0:
             return None
         ph, geo = self._ph, self._geo
-        T = self._mean_reservoir_T() if T is None else float(T)
-        tau = FP.lifetimes(ph, T) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
-        qv = ph.number_of_qpoints * ph.volume_unitcell
-        c = KN.heat_capacity(ph.omega, T, qv, self.hbar, self.kb)
-        src = KN.source_facets(geo.bound_cond)
-        pair = KN.parallel_pair(src, geo.facets_normal, geo.facets_area, geo.facet_centroid)
+        k = self._kinetic_inputs(T, tau)
+        tau, c, pair = k['tau'], k['c'], k['pair']
         B = int(batches)
         if B < 1:
             raise ValueError('kinetic_flights: batches = %d must be at least 1' % B)
@@ -610,26 +640,12 @@ class Population(Constants):
                     table, G, edges = KG.build(kind, G, ph, tau, ph.group_vel, axis)
                 else:
                     table = KG.check_table(groups[1], G, np.ravel(ph.omega).shape[0])
-            nb = -(-int(n) // B)
-            # one call: the caller's seed as it is (0 = the engine's own, which is the run's).  Batches need B different, known
-            # seeds: seed, seed + 1, ..; for seed 0 they start at the run's seed, the one the engine would have used
-            seeds = [int(seed)] if B == 1 else [(int(seed) or self.seed) + b for b in range(B)]
-            per = [self.engine.kinetic_flights(tau, c, n=nb, max_events=int(max_events), seed=s_,
-                                               groups=None if table is None else (G, table)) for s_ in seeds]
-            res = per[0] if B == 1 else KG.pool(per)
-        T_f = np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src])
-        omega_c = FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb)
-        s = KN.summarise(res, c, ph.group_vel, tau, T, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,
-                         geo.subvol_volume, pair=pair, omega_c=omega_c, qv=qv)
-        self.kinetic_last = s
-        line = KN.left_out_warning(s)                # (one call or the pooled batches: the files below are written all the same)
-        if line:
-            print(line)
+            per, res = self._kinetic_batches(k, n, B, max_events, seed, KG.pool, groups=None if table is None else (G, table))
+        s = self._kinetic_summary(res, k)            # (one call or the pooled batches: the files below are written all the same)
         sg = None
         if table is not None:
-            sg = KG.summarise_groups(res, c, ph.group_vel, tau, np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src], T_f,
-                                     geo.subvol_volume, table, G, pair=pair, omega_c=omega_c, qv=qv, kind=kind, edges=edges,
-                                     batches=per if B > 1 else None)
+            sg = KG.summarise_groups(res, c, ph.group_vel, tau, k['areas'], k['normals_in'], k['T_f'], geo.subvol_volume, table, G, pair=pair,
+                                     omega_c=k['omega_c'], qv=k['qv'], kind=kind, edges=edges, batches=per if B > 1 else None)
             self.kinetic_groups_last = sg
         if write and self.results_folder_name:
             KN.write_k_kinetic(KN.k_kinetic_path(self.results_folder_name), s)
@@ -660,30 +676,16 @@ class Population(Constants):
         B = int(batches)
         if B < 1:
             raise ValueError('kinetic_map: batches = %d must be at least 1' % B)
-        T = self._mean_reservoir_T() if T is None else float(T)
-        tau = FP.lifetimes(ph, T) if tau is None else np.asarray(tau, dtype=np.float64).ravel()
-        qv = ph.number_of_qpoints * ph.volume_unitcell
-        c = KN.heat_capacity(ph.omega, T, qv, self.hbar, self.kb)
-        src = KN.source_facets(geo.bound_cond)
-        pair = KN.parallel_pair(src, geo.facets_normal, geo.facets_area, geo.facet_centroid)
+        k = self._kinetic_inputs(T, tau)
+        T, tau, c = k['T'], k['tau'], k['c']
         lo, h, nc = FD.grid_from_bounds(geo.bounds, n_cells)
-        nb = -(-int(n) // B)
-        seeds = [int(seed)] if B == 1 else [(int(seed) or self.seed) + b for b in range(B)]
-        per = [self.engine.kinetic_flights(tau, c, n=nb, max_events=int(max_events), seed=s_, grid=(lo, h, nc)) for s_ in seeds]
-        res = per[0] if B == 1 else KM.pool(per)
-        T_f = np.array([float(geo.res_values[list(geo.res_facets).index(f)]) for f in src])
-        areas, normals_in = np.asarray(geo.facets_area)[src], -np.asarray(geo.facets_normal)[src]
-        s = KN.summarise(res, c, ph.group_vel, tau, T, areas, normals_in, T_f, geo.subvol_volume, pair=pair,
-                         omega_c=FP.mode_heat_capacity(np.ravel(ph.omega), T, self.hbar, self.kb), qv=qv)
-        self.kinetic_last = s
-        line = KN.left_out_warning(s)
-        if line:
-            print(line)
+        per, res = self._kinetic_batches(k, n, B, max_events, seed, KM.pool, grid=(lo, h, nc))
+        s = self._kinetic_summary(res, k)
         V = None
         if volume == 'solid':
             from .engine import cell_solid_volume
             V = cell_solid_volume(geo.mesh.vertices, geo.mesh.faces, lo, h, nc, device=int(getattr(self.args, 'device', [0])[0]))
-        m = KM.summarise_map(res, c, ph.group_vel, tau, areas, normals_in, T_f, lo, h, nc, volume=volume, solid_volume=V,
+        m = KM.summarise_map(res, c, ph.group_vel, tau, k['areas'], k['normals_in'], k['T_f'], lo, h, nc, volume=volume, solid_volume=V,
                              batches=per if B > 1 else None)
         m.update(T_flights=T, summary=s)
         self.kinetic_map_last = m

@@ -1,7 +1,9 @@
 """Kinetic flights on the CPU: the rule of nk_kinetic_flights (DESIGN.md "Kinetic flights") restated in NumPy, vectorised over the
 rays, with the oracle's ray cast (nko_find_boundary), its classifier (nko_classify) and its random numbers (Philox4x32-10 restated
-here over arrays; test_kinetic_host.py holds it against nko_uniform2).  What the GPU tests hold the kernel against, and the cases
-they share.  Test infrastructure: nothing under nanokappa_amd/ knows of it.
+here over arrays; test_kinetic_host.py holds it against nko_uniform2).  The rule stands here once, for all three entries: restate()
+is the plain call, restate(groups=...) adds the group tally of nk_kinetic_flights_groups and restate(grids=...) the map tally of
+nk_kinetic_flights_map to the same loop (kinetic_group_cases.py and kinetic_map_cases.py name their results).  What the GPU tests
+hold the kernel against, and the cases they share.  Test infrastructure: nothing under nanokappa_amd/ knows of it.
 
 The draws (nanokappa_amd/csrc/nk_kinetic.h), all uniform2(seed, ray id, k, tag) -> (a, b), ray id = (source << 32) | sample, k = the
 ray's event count when the draw is made:
@@ -108,6 +110,13 @@ def _over(term, B, src, F):
     return np.bincount(np.asarray(src)[~(np.abs(np.asarray(term, dtype=np.float64)) <= B)], minlength=F).astype(np.int64)
 
 
+def columns(table, G):
+    """The column of every mode in a group tally: its group, or G (the rest column) where the table holds -1."""
+    t = np.asarray(table, dtype=np.int64).ravel()
+    assert t.min() >= -1 and t.max() < G
+    return np.where(t < 0, int(G), t)
+
+
 def bounds(g, tau, vg, cdf_scatter, n, max_events):
     """nk_kinetic_flights' bounds and scales: dict B_t, B_x, k_t, k_x, k_T, k_D, k_D2 (and the per-ray bounds BT, BD, BD2)."""
     b = np.asarray(g['bounds'], dtype=np.float64).reshape(2, 3)
@@ -126,14 +135,22 @@ def bounds(g, tau, vg, cdf_scatter, n, max_events):
     return out
 
 
-def restate(g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=None, J=None, fused=True, cosine=True, tallies=True, trace=None):
+def restate(g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=None, J=None, fused=True, cosine=True, tallies=True, trace=None,
+            groups=(), grids=()):
     """The rule for n rays from every 'T' facet of the mesh tables g.  sv: the oracle's subvolume struct; c [M] the volumetric heat
     capacities; rough as free_path_cases.restate.  fused: positions by one fused multiply-add (the kernel's) or by a product and a
     sum.  cosine=False switches the cosine rejection off (any mode that flies inwards is accepted): the power check of the
     isothermal test.  trace: a dict that receives the counts of the segments sat out in a mode with v = 0 ('sitting'), of the specular
     turns ('turns'), of those into a mode with tau <= 0 ('dead_turns') and of the segments' terms left out, over all sources ('left_out_t',
     'left_out_x').  Returns the dict of Engine.kinetic_flights with rays=True
-    (without `report`'s device figures)."""
+    (without `report`'s device figures).
+    groups: a sequence of (table, G) -- a segment's four integers also go to (source, subvolume, column of the mode the segment was
+    flown in) of every table (DESIGN.md "Kinetic groups"); the dict then holds `groups`, the list of their [F, S, G + 1, 4] int64.
+    grids: a sequence of ((lo, h, n_cells), start_point) -- the four integers also go to (source, cell of the segment's point x_p) on
+    every grid, the cell by nanokappa_amd.field.cell_index (DESIGN.md "Kinetic maps"); start_point=True bins the segment's START
+    point x instead: the WRONG rule, for the sensitivity check of the isothermal test.  The dict then holds `grids`, the list of
+    (map [F, nx, ny, nz, 4] int64, clamped [F]).  kinetic_group_cases.restate_grouped and kinetic_map_cases.restate_map name them."""
+    from nanokappa_amd import field as FD
     from nanokappa_amd import kinetic as KN
     mesh = O.make_mesh(g)
     vg = np.asarray(group_vel, dtype=np.float64).reshape(-1, 3)
@@ -155,6 +172,13 @@ def restate(g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=No
     sidx = np.repeat(np.arange(F), n)
     rid = (sidx.astype(np.uint64) << np.uint64(32)) | np.tile(np.arange(n, dtype=np.uint64), F)
     zero = np.zeros(R, dtype=np.int64)
+    assert tallies or not (groups or grids)
+    gt = [(columns(t_, G_), np.zeros((F, S, int(G_) + 1, 4), dtype=np.int64)) for t_, G_ in groups]      # (column of every mode, grp)
+    mt = []                                                 # (lo, h, n_cells, start_point, map [F, ncells, 4], clamped [F])
+    for (lo_, h_, n_), sp_ in grids:
+        n_ = tuple(int(k_) for k_ in n_)
+        mt.append((np.asarray(lo_, dtype=np.float64), np.asarray(h_, dtype=np.float64), n_, bool(sp_),
+                   np.zeros((F, n_[0] * n_[1] * n_[2], 4), dtype=np.int64), np.zeros(F, dtype=np.int64)))
     # emission
     uf, us = uniform2(seed, rid, zero, TAG_KIN + 0)
     ur, _ = uniform2(seed, rid, zero, TAG_KIN + 1)
@@ -193,23 +217,34 @@ def restate(g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=No
         miss = flies & (fc < 0)
         end[act[miss]] = END_MISSED
         go = ~miss
-        i, v, ts, tc, fc, up, flies = act[go], v[go], ts[go], tc[go], fc[go], up[go], flies[go]
+        i, v, ts, tc, fc, up, flies, m = act[go], v[go], ts[go], tc[go], fc[go], up[go], flies[go], m[go]
         scat = ~flies | (ts < tc)
         seen['sitting'] += int((~flies).sum())
         t = np.where(scat, ts, tc)
         D[i] = fma(t[:, None], v, D[i])
         T[i] = T[i] + t
         if tallies:
-            s = classify(sv, _pos(up * t, v, x[i], fused))
+            xp = _pos(up * t, v, x[i], fused)               # the one uniform point of the segment: subvolume AND cell
+            s = classify(sv, xp)
             qt, o = _q(t, st, bd['B_t'])
             seen['left_out_t'] += o
             ovSt += _over(t, bd['B_t'], sidx[i], F)
-            np.add.at(sub[:, :, 0], (sidx[i], s), qt)
+            q4 = [qt]
             for a in range(3):
                 qa, o = _q(t * v[:, a], sx, bd['B_x'])
                 seen['left_out_x'] += o
                 ovSx += _over(t * v[:, a], bd['B_x'], sidx[i], F)
-                np.add.at(sub[:, :, 1 + a], (sidx[i], s), qa)
+                q4.append(qa)
+            for w in range(4):
+                np.add.at(sub[:, :, w], (sidx[i], s), q4[w])
+                for col, grp in gt:                         # m: the mode the segment was flown in (the event below may change it)
+                    np.add.at(grp[:, :, :, w], (sidx[i], s, col[m]), q4[w])
+            for lo_, h_, n_, sp_, mp, cl in mt:
+                ci, out = FD.cell_index(x[i] if sp_ else xp, lo_, h_, n_)
+                cell = (ci[:, 0] * n_[1] + ci[:, 1]) * n_[2] + ci[:, 2]
+                for w in range(4):
+                    np.add.at(mp[:, :, w], (sidx[i], cell), q4[w])
+                cl += np.bincount(sidx[i][out], minlength=F)
         k[i] += 1
         hp = _pos(t, v, x[i], fused)
         hsh[i] = hsh[i] * np.uint64(1000003) + np.where(scat, 1, fc + 2).astype(np.uint64)
@@ -276,12 +311,17 @@ def restate(g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=No
     sh = (F, n)
     rep = dict(bd, rays=R, events=int(k.sum()), casts=int(ncast.sum()), lost=int((end == END_LOST).sum()), missed=int((end == END_MISSED).sum()),
                capped=int((end == END_CAPPED).sum()), overflow=int(rows[:, 20:25].sum()), n_sources=F, n_subvolumes=S, source_facet=list(src))
-    return dict(n=n, source_facet=src, ends=rows[:, :F].copy(), lost=rows[:, 8].copy(), missed=rows[:, 9].copy(), capped=rows[:, 10].copy(),
-                events=rows[:, 11].copy(), casts=rows[:, 12].copy(), D=rows[:, 13:16] / sD, D2=rows[:, 16:19] / sD2, dwell_total=rows[:, 19] / sT,
-                dwell=sub[:, :, 0] / st, flux=sub[:, :, 1:4] / sx, rows=rows, sub=sub, cdf_scatter=cs, cdf_flux=cf, report=rep,
-                ray_x0=x0.reshape(sh + (3,)), ray_mode=mode0.reshape(sh).astype(np.int32), ray_end=end.reshape(sh).astype(np.int32),
-                ray_events=k.reshape(sh).astype(np.int32), ray_casts=ncast.reshape(sh).astype(np.int32), ray_D=D.reshape(sh + (3,)),
-                ray_dwell=T.reshape(sh), ray_hash=hsh.reshape(sh))
+    res = dict(n=n, source_facet=src, ends=rows[:, :F].copy(), lost=rows[:, 8].copy(), missed=rows[:, 9].copy(), capped=rows[:, 10].copy(),
+               events=rows[:, 11].copy(), casts=rows[:, 12].copy(), D=rows[:, 13:16] / sD, D2=rows[:, 16:19] / sD2, dwell_total=rows[:, 19] / sT,
+               dwell=sub[:, :, 0] / st, flux=sub[:, :, 1:4] / sx, rows=rows, sub=sub, cdf_scatter=cs, cdf_flux=cf, report=rep,
+               ray_x0=x0.reshape(sh + (3,)), ray_mode=mode0.reshape(sh).astype(np.int32), ray_end=end.reshape(sh).astype(np.int32),
+               ray_events=k.reshape(sh).astype(np.int32), ray_casts=ncast.reshape(sh).astype(np.int32), ray_D=D.reshape(sh + (3,)),
+               ray_dwell=T.reshape(sh), ray_hash=hsh.reshape(sh))
+    if gt:
+        res['groups'] = [t_[1] for t_ in gt]
+    if mt:
+        res['grids'] = [(t_[4].reshape((F,) + t_[2] + (4,)), t_[5]) for t_ in mt]
+    return res
 
 
 # ------------------------------------------------------------------------------------------- cases

@@ -1,173 +1,25 @@
-"""Kinetic groups on the CPU: the rule of kinetic_cases.restate with the group tally added (DESIGN.md "Kinetic groups") -- a segment's
-four words also go to the column of the mode the segment was flown in, the last column taking the modes whose table entry is -1.
-What the GPU tests hold nk_kinetic_flights_groups against, the tables they share and the per-group isothermal check.  The flight
-loop is kinetic_cases.restate's, restated here (kinetic_cases.py is not edited); test_kinetic_groups_host.py holds the two against
-each other bit for bit.  Test infrastructure: nothing under nanokappa_amd/ knows of it."""
-import math
-
+"""Kinetic groups on the CPU: the group tally of the kinetic flights (DESIGN.md "Kinetic groups") -- a segment's four words also go
+to the column of the mode the segment was flown in, the last column taking the modes whose table entry is -1.  The rule, tally
+included, stands once, in kinetic_cases.restate(groups=...); restate_grouped here names its results.  What the GPU tests hold
+nk_kinetic_flights_groups against, the tables they share and the per-group isothermal check.  Test infrastructure: nothing under
+nanokappa_amd/ knows of it."""
 import numpy as np
 
 import kinetic_cases as K
 import free_path_cases as FC
-from free_path_cases import O, cached, fma
-from kinetic_cases import TAG_KIN, TAG_FREE, END_LOST, END_MISSED, END_CAPPED, ROW_WORDS, MAX_EVENTS
+from free_path_cases import cached
+from kinetic_cases import MAX_EVENTS, columns
 
 
-def columns(table, G):
-    """The column of every mode: its group, or G (the rest column) where the table holds -1."""
-    t = np.asarray(table, dtype=np.int64).ravel()
-    assert t.min() >= -1 and t.max() < G
-    return np.where(t < 0, int(G), t)
-
-
-def restate_grouped(table, G, g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=None, J=None, fused=True, more=()):
+def restate_grouped(table, G, g, sv, group_vel, tau, c, n, seed=0, max_events=MAX_EVENTS, rough=None, J=None, fused=True, more=(),
+                    cosine=True, trace=None):
     """kinetic_cases.restate(g, sv, group_vel, tau, c, n, ...) with the group tally: returns its dict and grp [F, S, G + 1, 4] int64,
     dwell_g, flux_g.  more: further (table, G) pairs tallied over the same flights -> `grp_more`, a list of their grp arrays."""
-    from nanokappa_amd import kinetic as KN
-    mesh = O.make_mesh(g)
-    vg = np.asarray(group_vel, dtype=np.float64).reshape(-1, 3)
-    tau = np.asarray(tau, dtype=np.float64).ravel()
-    M = vg.shape[0]
-    cs, cf = KN.tables(c, tau, vg)
-    bc, trans, ridx = FC.facet_tables(g, rough)
-    src = KN.source_facets(g['bound_cond'])
-    F = src.shape[0]
-    S = int(sv.S)
-    src_of = -np.ones(bc.shape[0], dtype=np.int64)
-    src_of[src] = np.arange(F)
-    off, flat, fcdf = K.facet_faces(g)
-    verts = np.asarray(g['vertices'], dtype=np.float64)[np.asarray(g['faces'], dtype=int)]
-    n_in_facet = -np.asarray(g['facets_normal'], dtype=np.float64)
-    bd = K.bounds(g, tau, vg, cs, n, max_events)
-    st, sx = 2.0 ** bd['k_t'], 2.0 ** bd['k_x']
-    R = F * n
-    sidx = np.repeat(np.arange(F), n)
-    rid = (sidx.astype(np.uint64) << np.uint64(32)) | np.tile(np.arange(n, dtype=np.uint64), F)
-    zero = np.zeros(R, dtype=np.int64)
-    tallies = [(columns(t_, G_), np.zeros((F, S, int(G_) + 1, 4), dtype=np.int64)) for t_, G_ in ((table, G),) + tuple(more)]
-    # emission
-    uf, us = K.uniform2(seed, rid, zero, TAG_KIN + 0)
-    ur, _ = K.uniform2(seed, rid, zero, TAG_KIN + 1)
-    x = np.zeros((R, 3))
-    for f in range(F):
-        r = np.nonzero(sidx == f)[0]
-        f0, nf = off[src[f]], off[src[f] + 1] - off[src[f]]
-        a = np.minimum(np.searchsorted(fcdf[f0:f0 + nf], uf[r], side='right'), nf - 1)
-        fv = verts[flat[f0 + a]]
-        sq = np.sqrt(us[r])
-        a0, a1, a2 = 1.0 - sq, (1.0 - ur[r]) * sq, ur[r] * sq
-        x[r] = (a0[:, None] * fv[:, 0] + a1[:, None] * fv[:, 1]) + a2[:, None] * fv[:, 2]
-    x0 = x.copy()
-    mode = K._emit(seed, rid, zero, n_in_facet[src[sidx]], vg, cf)
-    mode0 = mode.copy()
-    end = np.where(mode < 0, END_LOST, 0).astype(np.int64)
-    k, ncast = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
-    D, T = np.zeros((R, 3)), np.zeros(R)
-    hsh = np.zeros(R, dtype=np.uint64)
-    sub = np.zeros((F, S, 4), dtype=np.int64)
-    ovSt, ovSx = np.zeros(F, dtype=np.int64), np.zeros(F, dtype=np.int64)       # the segments' terms left out, by source
-    act = np.nonzero(mode >= 0)[0]
-    while act.size:
-        m = mode[act]
-        v, t_m = vg[m], tau[m]
-        u, up = K.uniform2(seed, rid[act], k[act], TAG_KIN + 2)
-        u = np.where(u > 0.0, u, 2.0 ** -54)
-        ts = -t_m * np.log(u)
-        flies = (v != 0).any(axis=1)
-        tc, fc = np.full(act.shape[0], np.inf), -np.ones(act.shape[0], dtype=np.int64)
-        if flies.any():
-            a, b = FC.find_boundary(mesh, x[act[flies]], v[flies])
-            tc[flies], fc[flies] = a, b
-            ncast[act[flies]] += 1
-        miss = flies & (fc < 0)
-        end[act[miss]] = END_MISSED
-        go = ~miss
-        i, v, ts, tc, fc, up, flies, m = act[go], v[go], ts[go], tc[go], fc[go], up[go], flies[go], m[go]
-        scat = ~flies | (ts < tc)
-        t = np.where(scat, ts, tc)
-        D[i] = fma(t[:, None], v, D[i])
-        T[i] = T[i] + t
-        s = K.classify(sv, K._pos(up * t, v, x[i], fused))
-        qt, _ = K._q(t, st, bd['B_t'])
-        ovSt += K._over(t, bd['B_t'], sidx[i], F)
-        q4 = [qt]
-        for a in range(3):
-            qa, _ = K._q(t * v[:, a], sx, bd['B_x'])
-            ovSx += K._over(t * v[:, a], bd['B_x'], sidx[i], F)
-            q4.append(qa)
-        for w in range(4):
-            np.add.at(sub[:, :, w], (sidx[i], s), q4[w])
-            for col, grp in tallies:                        # m: the mode the segment was flown in (the event below may change it)
-                np.add.at(grp[:, :, :, w], (sidx[i], s, col[m]), q4[w])
-        k[i] += 1
-        hp = K._pos(t, v, x[i], fused)
-        hsh[i] = hsh[i] * np.uint64(1000003) + np.where(scat, 1, fc + 2).astype(np.uint64)
-        now = scat.copy()
-        x[i[scat]] = hp[scat]
-        alive = np.ones(i.shape[0], dtype=bool)
-        b = np.where(scat, 0, bc[np.maximum(fc, 0)])
-        res = b == ord('T')
-        end[i[res]] = src_of[fc[res]]
-        alive[res] = False
-        per = b == ord('P')
-        x[i[per]] = hp[per] + trans[fc[per]]
-        ro = np.nonzero(b == ord('R'))[0]
-        if ro.size:
-            r0, r1 = K.uniform2(seed, rid[i[ro]], k[i[ro]], TAG_FREE + 3)
-            f = ridx[fc[ro]]
-            mr = mode[i[ro]]
-            out = np.where(f >= 0, np.asarray(rough['spec_map'])[np.maximum(f, 0), mr], -1).astype(np.int64)
-            spec = (f >= 0) & np.asarray(rough['true_spec'])[np.maximum(f, 0), mr].astype(bool) & \
-                (r0 <= np.asarray(rough['specularity'])[np.maximum(f, 0), mr]) & (out >= 0) & (out < M)
-            x[i[ro]] = hp[ro]
-            dj = rough.get('degen_j2')
-            if dj is not None:
-                j2 = np.asarray(dj, dtype=np.int64)[np.maximum(out, 0)]
-                out = np.where(spec & (j2 > -1) & (j2 < J) & (r1 >= 0.5), (out // J) * J + j2, out)
-            sp_i = ro[spec]
-            mode[i[sp_i]] = out[spec]
-            now[sp_i] = ~(tau[out[spec]] > 0.0)
-            df = ro[~spec]
-            if df.size:
-                mnew = K._emit(seed, rid[i[df]], k[i[df]], n_in_facet[fc[df]], vg, cf)
-                mode[i[df]] = mnew
-                lost = mnew < 0
-                end[i[df[lost]]] = END_LOST
-                alive[df[lost]] = False
-        if now.any():
-            us2, _ = K.uniform2(seed, rid[i[now]], k[i[now]], TAG_KIN + 3)
-            mode[i[now]] = np.minimum(np.searchsorted(cs, us2, side='right'), M - 1)
-        cap = alive & (k[i] >= max_events)
-        end[i[cap]] = END_CAPPED
-        alive[cap] = False
-        act = i[alive]
-    rows = np.zeros((F, ROW_WORDS), dtype=np.int64)
-    sD, sD2, sT = 2.0 ** bd['k_D'], 2.0 ** bd['k_D2'], 2.0 ** bd['k_T']
-    for f in range(F):
-        r = sidx == f
-        for e in range(F):
-            rows[f, e] = int((end[r] == e).sum())
-        rows[f, 8], rows[f, 9], rows[f, 10] = (int((end[r] == c_).sum()) for c_ in (END_LOST, END_MISSED, END_CAPPED))
-        rows[f, 11], rows[f, 12] = int(k[r].sum()), int(ncast[r].sum())
-        for a in range(3):
-            q, o = K._q(D[r, a], sD, bd['BD'])
-            rows[f, 13 + a], rows[f, 20] = q.sum(), rows[f, 20] + o
-            q, o = K._q(D[r, a] * D[r, a], sD2, bd['BD2'])
-            rows[f, 16 + a], rows[f, 21] = q.sum(), rows[f, 21] + o
-        q, o = K._q(T[r], sT, bd['BT'])
-        rows[f, 19], rows[f, 22] = q.sum(), o
-    rows[:, 23], rows[:, 24] = ovSt, ovSx
-    sh = (F, n)
-    rep = dict(bd, rays=R, events=int(k.sum()), casts=int(ncast.sum()), lost=int((end == END_LOST).sum()), missed=int((end == END_MISSED).sum()),
-               capped=int((end == END_CAPPED).sum()), overflow=int(rows[:, 20:25].sum()), n_sources=F, n_subvolumes=S, source_facet=list(src))
-    grp = tallies[0][1]
-    return dict(n=n, source_facet=src, ends=rows[:, :F].copy(), lost=rows[:, 8].copy(), missed=rows[:, 9].copy(), capped=rows[:, 10].copy(),
-                events=rows[:, 11].copy(), casts=rows[:, 12].copy(), D=rows[:, 13:16] / sD, D2=rows[:, 16:19] / sD2, dwell_total=rows[:, 19] / sT,
-                dwell=sub[:, :, 0] / st, flux=sub[:, :, 1:4] / sx, rows=rows, sub=sub, cdf_scatter=cs, cdf_flux=cf, report=rep,
-                ray_x0=x0.reshape(sh + (3,)), ray_mode=mode0.reshape(sh).astype(np.int32), ray_end=end.reshape(sh).astype(np.int32),
-                ray_events=k.reshape(sh).astype(np.int32), ray_casts=ncast.reshape(sh).astype(np.int32), ray_D=D.reshape(sh + (3,)),
-                ray_dwell=T.reshape(sh), ray_hash=hsh.reshape(sh), grp=grp, dwell_g=grp[..., 0] / st, flux_g=grp[..., 1:4] / sx,
-                grp_more=[t_[1] for t_ in tallies[1:]])
+    r = K.restate(g, sv, group_vel, tau, c, n, seed=seed, max_events=max_events, rough=rough, J=J, fused=fused, cosine=cosine, trace=trace,
+                  groups=((table, G),) + tuple(more))
+    grp = r.pop('groups')
+    return dict(r, grp=grp[0], dwell_g=grp[0][..., 0] / 2.0 ** r['report']['k_t'], flux_g=grp[0][..., 1:4] / 2.0 ** r['report']['k_x'],
+                grp_more=grp[1:])
 
 
 # ------------------------------------------------------------------------------------------- tables and cases

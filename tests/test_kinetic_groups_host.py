@@ -14,7 +14,7 @@ from nanokappa_amd import field_groups as FG
 
 @pytest.mark.parametrize('name', sorted(K.PARITY))
 def test_restatement_against_restatement(name):
-    """The duplicated loop: every key of K.restate bit for bit, and the columns sum to sub."""
+    """The group tally does not disturb the flights: every key of K.restate without it bit for bit, and the columns sum to sub."""
     ref, got = K.parity_run(name), KGC.parity_run(name)
     for k, v in ref.items():
         if k == 'report':

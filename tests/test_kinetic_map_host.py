@@ -19,7 +19,8 @@ def cell_sum(m):
 
 @pytest.mark.parametrize('name', sorted(K.PARITY))
 def test_restatement_against_restatement(name):
-    """The duplicated loop: every key of K.restate bit for bit (rows but for word 25), and the cells sum to the subvolumes."""
+    """The map tally does not disturb the flights: every key of K.restate without it bit for bit (rows but for word 25), and the
+    cells sum to the subvolumes."""
     ref, got = K.parity_run(name), KMC.parity_run(name)
     for k, v in ref.items():
         if k == 'report':
