@@ -455,7 +455,10 @@ typedef struct {
     double seconds;              /* device time of the kernel, from HIP events */
 } nk_free_path_report;
 /* NK_ERR_ARG, with a text that names the cause: no material or mesh, 'R' facets without rough tables (nk_set_rough /
- * nk_rough_finish), no x0 on a mesh that was set without its volume tables, n_samples <= 0, a mode out of range, tau NULL. */
+ * nk_rough_finish), no x0 on a mesh that was set without its volume tables, n_samples <= 0, a mode out of range, tau NULL, a
+ * lifetime that is positive and not finite in any entry of tau ("tau of mode m is not finite"; a lifetime that is not positive -- 0,
+ * negative, -inf, NaN -- is a mode that does not live and is taken), a coordinate of x0 that is not finite ("x0 of list entry i,
+ * sample s is not finite").  Nothing is launched or allocated then and the report is all zero. */
 int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *args, const nk_free_path_modes *modes, const nk_free_path_rays *rays,
                   nk_free_path_report *report);
 /* The report of the last call; all zero on a context that never made one (nothing was launched or allocated). */
@@ -489,7 +492,8 @@ typedef struct {
     double seconds;              /* device time of the launches, from HIP events */
 } nk_free_path_columns_report;
 /* NK_ERR_ARG, with a text that names the cause: n_columns outside 1 .. NK_FREE_PATH_MAX_COLUMNS, and every refusal of
- * nk_free_paths, in its words; nothing is launched or allocated then and the report is all zero. */
+ * nk_free_paths, in its words (a lifetime in any of the n_columns tables; with more than one the text adds "(column c)"); nothing
+ * is launched or allocated then and the report is all zero. */
 int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *args, int32_t n_columns, const nk_free_path_modes *modes,
                           const nk_free_path_rays *rays, nk_free_path_columns_report *report);
 

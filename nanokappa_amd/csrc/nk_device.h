@@ -363,7 +363,11 @@ __device__ __forceinline__ double nk_fma_c(double p, double r, double c) {
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(p), "v"(r), "v"(c));
     return o;
 }
+// Below -800 the result is +0 whatever x is (exp(-745.2) is half the smallest subnormal), and the reduction must not see such an
+// x: from 1e18 on rint(x log2 e) no longer fits the two-part ln 2, r is no longer small and the polynomial overflows before the
+// ldexp (-0.0 at -1e18, +-inf at -1e45 and -1e100, NaN at -inf).  One compare and select; a NaN passes through.
 __device__ __forceinline__ double nk_exp(double x) {
+    x = x < -800.0 ? -800.0 : x;
     const double k = __builtin_rint(x * 1.4426950408889634);
     double r = __builtin_fma(-k, 6.93147180369123816490e-01, x);
     r = __builtin_fma(-k, 1.90821492927058770002e-10, r);

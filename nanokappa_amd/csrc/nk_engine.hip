@@ -3936,9 +3936,10 @@ int nk_build_enter_prob(nk_ctx *ctx, int32_t R, const double *normal_in, const d
 // What nk_free_paths, nk_free_paths_columns and nk_free_paths_map share.  A call weighs its rays with K lifetime tables: K = 1
 // for the plain call and the map, the leading axis of tau, of the rows and of the per-ray outputs (but x0) for the columns.
 
-// The refusals, in the words of the entry point `who`; tau_holds: what its message says a->tau is.  Sets the list's length and
-// the ray count.
-static int nk_free_refuse(nk_ctx *ctx, const std::string &who, const nk_free_path_args *a, const char *tau_holds, int64_t &nlist, int64_t &rays) {
+// The refusals, in the words of the entry point `who`; tau_holds: what its message says a->tau is, K its tables.  Sets the list's
+// length and the ray count.  A lifetime lives when it is positive, and then it must be finite (W tau g with tau = inf is inf 0);
+// the start points must be finite: neither reaches a kernel.
+static int nk_free_refuse(nk_ctx *ctx, const std::string &who, const nk_free_path_args *a, const char *tau_holds, int64_t K, int64_t &nlist, int64_t &rays) {
     NK_ARG(ctx->have_material, who + ": no material (nk_set_material first)");
     NK_ARG(ctx->have_mesh, who + ": no mesh (nk_set_mesh first)");
     const NkDev &d = ctx->d;
@@ -3957,6 +3958,13 @@ static int nk_free_refuse(nk_ctx *ctx, const std::string &who, const nk_free_pat
     NK_ARG(a->x0 || d.nS > 0, who + ": no start points (x0) and the mesh was set without its volume tables (simplices)");
     rays = nlist * (int64_t)a->n_samples;
     NK_ARG(rays < (1ll << 31), who + ": " + std::to_string((long long)rays) + " rays are more than one call takes (2^31)");
+    for (int64_t i = 0; i < K * (int64_t)d.M; ++i)
+        NK_ARG(!(a->tau[i] > 0.0) || std::isfinite(a->tau[i]), who + ": tau of mode " + std::to_string((long long)(i % d.M)) + " is not finite" +
+                                                                   (K > 1 ? " (column " + std::to_string((long long)(i / d.M)) + ")" : std::string()));
+    if (a->x0)
+        for (int64_t i = 0; i < rays * 3; ++i)
+            NK_ARG(std::isfinite(a->x0[i]), who + ": x0 of list entry " + std::to_string((long long)(i / 3 / a->n_samples)) + ", sample " +
+                                                std::to_string((long long)(i / 3 % a->n_samples)) + " is not finite");
     return NK_OK;
 }
 
@@ -4059,7 +4067,7 @@ int nk_free_paths(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_path_mo
     if (rep) memset(rep, 0, sizeof(*rep));
     NK_ARG(ctx && a, "nk_free_paths: NULL argument");
     int64_t nlist, rays;
-    NK_TRY(nk_free_refuse(ctx, "nk_free_paths", a, "the lifetimes of all Q*J modes at the temperature of the estimate", nlist, rays));
+    NK_TRY(nk_free_refuse(ctx, "nk_free_paths", a, "the lifetimes of all Q*J modes at the temperature of the estimate", 1, nlist, rays));
     NK_HIP(hipSetDevice(ctx->device));
     NkFreeCall call(ctx, a, pr, 1, nlist, rays);
     NK_HIP(call.err());
@@ -4091,7 +4099,7 @@ int nk_free_paths_columns(nk_ctx *ctx, const nk_free_path_args *a, int32_t n_col
     NK_ARG(n_columns >= 1 && n_columns <= NK_FREE_PATH_MAX_COLUMNS, "nk_free_paths_columns: n_columns = " + std::to_string(n_columns) +
                                                                         " must be 1 .. " + std::to_string(NK_FREE_PATH_MAX_COLUMNS));
     int64_t nlist, rays;
-    NK_TRY(nk_free_refuse(ctx, "nk_free_paths_columns", a, "per column the lifetimes of all Q*J modes", nlist, rays));
+    NK_TRY(nk_free_refuse(ctx, "nk_free_paths_columns", a, "per column the lifetimes of all Q*J modes", n_columns, nlist, rays));
     NK_HIP(hipSetDevice(ctx->device));
     const int64_t K = n_columns;
     const int ntiles = (int)((K + NK_FC_TILE - 1) / NK_FC_TILE);
@@ -4137,7 +4145,7 @@ int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_pat
     if (rep) memset(rep, 0, sizeof(*rep));
     NK_ARG(ctx && a && gr, "nk_free_paths_map: NULL argument");
     int64_t nlist, rays;
-    NK_TRY(nk_free_refuse(ctx, "nk_free_paths_map", a, "the lifetimes of all Q*J modes at the temperature of the estimate", nlist, rays));
+    NK_TRY(nk_free_refuse(ctx, "nk_free_paths_map", a, "the lifetimes of all Q*J modes at the temperature of the estimate", 1, nlist, rays));
     NkDev &d = ctx->d;
     // the map's own arguments
     NK_ARG(gr->weight, "nk_free_paths_map: weight is NULL (a weight vector per list entry, C_m v_m / (Q V))");
@@ -4158,8 +4166,7 @@ int nk_free_paths_map(nk_ctx *ctx, const nk_free_path_args *a, const nk_free_pat
     double lam = 0.0, tmax = 0.0;
     for (int64_t m = 0; m < d.M; ++m) {
         const double t = a->tau[m];
-        if (!(t > 0.0)) continue;
-        NK_ARG(std::isfinite(t), "nk_free_paths_map: tau of mode " + std::to_string((long long)m) + " is not finite");
+        if (!(t > 0.0)) continue;                               // (positive lifetimes are finite: nk_free_refuse)
         const double *v = &ctx->h_vg[3 * (size_t)m];
         const double vi = std::max(std::max(fabs(v[0]), fabs(v[1])), fabs(v[2]));
         lam = std::max(lam, vi * t);

@@ -11,7 +11,10 @@
 
 // g = -expm1(-a) and e = exp(-a), a >= 0.  Up to 1/8 the series a (1 - a/2 + a^2/6 - ...) through a^10 / 11! (the next term is
 // 2.4e-19 of the first); 1 - exp(-a) would lose the digits of a there (three of them at a = 2.5e-3, the common case: a flight
-// across a 200 A box against a lifetime of 1e3 ps).
+// across a 200 A box against a lifetime of 1e3 ps).  Above 1/8, 1 - nk_exp(-a) for every a up to +inf: nk_exp returns +0 below its
+// underflow point however far (it clamps its argument), so a positive lifetime of 5e-324 gives e = +0, g = 1 like any other that
+// the flight outlasts.  a is never NaN or negative here: tau > 0 and finite (nk_free_refuse), tc >= 0 from a cast that hit.
+// The seam a = 1/8 belongs to the series; both sides are good to 3e-18 there (tests/free_path_edge_cases.py 'seam').
 __device__ __forceinline__ void nk_fl_decay(double a, double &g, double &e) {
 #pragma clang fp contract(off)
     if (a <= 0.125) {

@@ -139,7 +139,7 @@ def restate(g, group_vel, tau, modes, n, x0=None, seed=0, max_segments=MAX_SEGME
     x = x0.copy()
     # modes that do not fly or do not live take no cast
     still = (tau[m0] > 0) & (np.abs(vg[m0]).max(axis=1) > 0)
-    T[~still] = np.maximum(tau[m0[~still]], 0.0)
+    T[~still] = np.where(tau[m0[~still]] > 0, tau[m0[~still]], 0.0)         # (the kernel's tau > 0 ? tau : 0: a NaN lifetime gives 0)
     p_int[~still] = 1.0
     act = np.nonzero(still)[0]
     while act.size:

@@ -57,7 +57,12 @@ def test_exp(eng300):
     hi, lo = exact(mp.exp, x)
     assert ulp_err(got, hi, lo, tag='nk_exp', bound=1.0) <= 1.0
     # far ends: nothing below the subnormals, infinity above the largest double
-    assert np.array_equal(eng300.eval('exp', np.array([-750.0, -1e3, -1e4])), np.zeros(3))
+    # ... +0, the sign bit clear, however far below: nk_exp clamps its argument at -800 (without that the reduction loses its meaning
+    # from -1e18 on and returned -0.0, +-inf and, for -inf, NaN: tests/test_free_path_edges_host.py restates it); NaN stays NaN
+    far = np.array([-750.0, -1e3, -1e4, -1e17, -1e18, -1e20, -1e40, -1e45, -1e100, -1e300, -np.inf])
+    low = eng300.eval('exp', far)
+    assert np.array_equal(low, np.zeros(far.shape[0])) and not np.signbit(low).any(), low
+    assert np.isnan(eng300.eval('exp', np.array([np.nan]))).all()
     assert np.array_equal(eng300.eval('exp', np.array([710.0])), [np.inf])
     # [-745, -700): (mostly) subnormal results, rounded once more by the ldexp: finite, non-negative, within two spacings
     xs = rng.uniform(-745.0, -700.0, 2000)
